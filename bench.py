@@ -6,20 +6,24 @@ Headline workload (default, `--workload c3`) = BASELINE.json configs[2], the con
 one "step" = one pass of the hot path over one such batch: 70 text tokens -> prefill of 103 rows -> 280 mel tokens (fixed-length
 mode) -> latent stash -> HiFi-GAN -> 312 064 samples per utterance, waveforms delivered to the host.  Weights (seeded
 synthetic, true shapes) and speaker conditioning are resident in HBM before the timed region.  The timed region runs the engine
-exactly as the parity tests do (profile mode OFF); the per-kernel roofline numbers come from a profile pass right after it (the
-same workload once more with aur_set_profile on: HIP events on the stream the kernels run on, see include/auralis_amd.h).
+exactly as the parity tests do (profile mode OFF).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if asked (--dump-outputs: DIR/tokens.npy,
+DIR/wav.npy, DIR/wav_positions.npy, see dump_outputs) and prints the line.  `--full` adds everything else, after the timed steps:
+the per-kernel roofline numbers from a profile pass (the same workload once more with aur_set_profile on: HIP events on the stream
+the kernels run on, see include/auralis_amd.h), the side workloads c3f, c2 and c5s (`--no-side` skips them; under torchrun with
+N > 1: c4), the CPU baseline (`--no-cpu-baseline`), the cross-rank checks of a multi-GPU run and the full report (`--out`).
 
 Other workloads: `--workload c3f` (the headline workload as 64 concurrent TTSRequests through the TTS facade: the drop-in boundary on
 the clock), `--workload c2` (configs[1]: ONE 200-char utterance, greedy, batch 1: time to audio), `--workload c5s` (configs[4]
 at single-GPU scale: one GPU's eighth of the ~450 k characters, mixed en/fr/de through longform.stream_longform, natural stop, ragged),
-`--workload c4` (configs[3]: 512 utterances dealt 64 at a time to the ranks by parallel.shard_units, strong scaling).  The default
-run also measures c3f, c2 and c5s once after the headline (`--no-side` skips them) and, under torchrun with N > 1, c4.
+`--workload c4` (configs[3]: 512 utterances dealt 64 at a time to the ranks by parallel.shard_units, strong scaling).
 
-Output: the LAST stdout line is one compact JSON object (< 4 KB: the contract fields + roofline + cpu_baseline + one summary per
-side workload); everything else goes to gpurun_out/bench_full.json and stderr.
+Output: the LAST stdout line is one compact JSON object (< 4 KB: the contract fields and, with --full, roofline + cpu_baseline + one
+summary per side workload); everything else goes to stderr and, with --full, to the full report (--out).
 
 Multi-GPU: utterances are independent, so each rank runs its own batches; the only collective is one RCCL broadcast of the speaker
 conditioning (133 120 B) from rank 0 before the timed region.
@@ -300,19 +304,23 @@ class Bench:
         torch.cuda.synchronize()
         self.eng.sync()
 
-    def run_batches(self, keys, batch=None, sampled=True):
+    def run_batches(self, keys, batch=None, sampled=True, keep=None):
         """one batch of `batch` utterances per key, one after the other; results consumed in place (views of the engine's pinned
-        result blocks: the D2H copies are part of the step), released once counted"""
+        result blocks: the D2H copies are part of the step), released once counted.  `keep` (a list): the results of the LAST
+        key's batch are appended to it in submission order instead of being released; the caller releases them"""
         a, eng = self.args, self.eng
         batch = batch or a.batch
         total = 0
         groups = [list(keys)] if a.pipeline else [[k] for k in keys]
+        last, kept = keys[-1], {}
         for grp in groups:
             t_grp = time.perf_counter()
             for k in grp:
                 for b in range(batch):
-                    eng.submit(self.text_ids, self.SPK, temperature=0.75 if sampled else 0.0, top_p=0.85, top_k=50, repetition_penalty=5.0,
-                               max_tokens=a.tokens, seed=(self.rank * 100003 + (k + 7) * 1009 + b), ignore_stop=True)
+                    sid = eng.submit(self.text_ids, self.SPK, temperature=0.75 if sampled else 0.0, top_p=0.85, top_k=50, repetition_penalty=5.0,
+                                     max_tokens=a.tokens, seed=(self.rank * 100003 + (k + 7) * 1009 + b), ignore_stop=True)
+                    if keep is not None and k == last:
+                        kept[sid] = b
             if os.environ.get("AUR_BENCH_STEP_TRACE"):   # host time of every aur_step of the batch: where the wall time outside the GPU phases goes
                 outs, marks, t_sub = [], [], time.perf_counter()
                 while True:
@@ -335,7 +343,10 @@ class Bench:
             total += sum(len(o["wav"]) for o in outs)
             for o in outs:
                 assert o["error"] == 0
-                eng.release(o["seq_id"])
+                if o["seq_id"] not in kept:
+                    eng.release(o["seq_id"])
+        if keep is not None:
+            keep.extend(sorted((o for o in outs if o["seq_id"] in kept), key=lambda o: kept[o["seq_id"]]))
         return total
 
     # -- c2: BASELINE configs[1], one utterance, greedy, batch 1 (the regime the reference publishes latencies for, README.md:483-485)
@@ -531,6 +542,34 @@ class Bench:
                 "ids_digest": hashlib.blake2b("".join(h for _, _, h in merged).encode(), digest_size=8).hexdigest()}
 
 
+DUMP_WAV_BYTES = 48 << 20   # --dump-outputs: at most this much of waveform (64 MB in all with the rest)
+
+
+def dump_outputs(out_dir, outs):
+    """What a caller of the timed path received for the last step's batch, in submission order (row b = seed index b):
+    tokens.npy  float32 [B, T]   the mel token ids (-1 pads a shorter sequence; fixed-length mode has none)
+    wav.npy     float32 [B, S]   the waveforms at the S positions of wav_positions.npy (all of them when B x samples fits
+                                 DUMP_WAV_BYTES, else a seeded sorted sample of positions, the same for every row; 0 past a row's end)
+    wav_positions.npy  float64 [S]"""
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(outs)
+    T = max(len(o["tokens"]) for o in outs)
+    L = max(len(o["wav"]) for o in outs)
+    tokens = np.full((B, T), -1.0, dtype=np.float32)
+    for b, o in enumerate(outs):
+        tokens[b, :len(o["tokens"])] = o["tokens"]
+    S = min(L, DUMP_WAV_BYTES // (4 * B))
+    pos = np.arange(L) if S == L else np.sort(np.random.default_rng(0).choice(L, size=S, replace=False))
+    wav = np.zeros((B, S), dtype=np.float32)
+    for b, o in enumerate(outs):
+        n = int(np.searchsorted(pos, len(o["wav"])))
+        wav[b, :n] = np.asarray(o["wav"])[pos[:n]]
+    np.save(os.path.join(out_dir, "tokens.npy"), tokens)
+    np.save(os.path.join(out_dir, "wav.npy"), wav)
+    np.save(os.path.join(out_dir, "wav_positions.npy"), pos.astype(np.float64))
+    _log(f"outputs of the last step -> {out_dir}: tokens {tokens.shape}, wav {wav.shape} of {B} x {L} samples")
+
+
 def compact(line, full_path):
     """The driver-facing line: contract fields + roofline + cpu_baseline + one summary per side workload, < 4 KB."""
     k = line["kernels"] or {}
@@ -613,8 +652,13 @@ def compact(line, full_path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (one batch of --batch utterances each)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the profile pass, the side workloads, the CPU baseline and the multi-GPU "
+                         "checks, and write the full report (--out); a plain run does none of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last step to DIR/*.npy (see dump_outputs)")
     ap.add_argument("--workload", choices=["c3", "c3f", "c2", "c5s", "c4"], default="c3",
                     help="c3 (default) = BASELINE configs[2], the headline; c3f (the same through the TTS facade) / c2 / c5s / c4 run only "
                          "that workload and print its record")
@@ -667,6 +711,8 @@ def main():
     ap.add_argument("--cpu-c1", action="store_true", help="also time BASELINE configs[0] on the CPU oracle")
     ap.add_argument("--out", default=os.path.join("gpurun_out", "bench_full.json"))
     args = ap.parse_args()
+    if args.steps < 1 and args.workload == "c3":
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line, the compact JSON record: everything native libraries print to file descriptor 1 (RCCL's
     # version banner at communicator creation, for one) is sent to stderr instead, and the record goes to the saved descriptor
@@ -756,11 +802,12 @@ def main():
     elif not use_dist:
         eng.set_conditioning(SPK, B.cond.numpy(), B.spk.numpy())
     if use_dist:
+        multi["bcast_route"] = route
+    if use_dist and args.full:
         # self-verification of the multi-GPU path, outside the timed region: (1) the voice every rank holds in device memory is
         # byte-identical to rank 0's; (2) the SAME small workload (same prompts, same seeds, greedy and sampled) produces
         # byte-identical ids and PCM on every rank (batch invariance makes that a requirement, not a hope)
         from auralis_amd.parallel import all_ranks_equal
-        multi["bcast_route"] = route
         multi["conditioning_hash_equal_across_ranks"] = all_ranks_equal(eng.conditioning_checksum(SPK))
         for k in range(4):
             eng.submit(B.make_ids(20 + 5 * k, 900 + k), SPK, temperature=(0.0 if k < 2 else 0.75),
@@ -800,13 +847,20 @@ def main():
         B.run_batches(range(-args.warmup, 0))
         _log(f"{args.warmup} warmup step(s) done")
     eng.reset_stats()
+    kept = [] if args.dump_outputs else None
     B.fence()
     t0 = time.perf_counter()
-    samples = B.run_batches(range(args.steps))
+    samples = B.run_batches(range(args.steps), keep=kept)
     _log(f"{args.steps} timed step(s) done at +{time.perf_counter() - t0:.3f}s")
     B.fence()
     dt = time.perf_counter() - t0
     st = eng.stats()
+    if kept is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, kept)
+        for o in kept:
+            eng.release(o["seq_id"])
+        del kept
 
     if use_dist:
         per_rank = [None] * world
@@ -821,7 +875,7 @@ def main():
 
     # ---- profile pass (every rank runs it, so that the ranks stay in step; rank 0 reports): the same batch once more with profile on
     kernels = None
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         eng.set_profile(args.profile_every)
         eng.reset_stats()
         ps = B.run_batches([args.steps + 1000])
@@ -862,7 +916,7 @@ def main():
             line["multi_gpu"] = multi
     # ---- side workloads
     c2 = c5 = c4 = c3f = None
-    if not args.no_side:
+    if args.full and not args.no_side:
         if world == 1:
             c3f = side("c3f", lambda: B.workload_c3f(max(1, min(args.steps, 10))))
             c2 = side("c2", B.workload_c2)
@@ -873,7 +927,7 @@ def main():
     # aur_broadcast_conditioning on the engine's own communicator and must arrive byte-identical to the first one.  Under a
     # watchdog: a hang ends in "timeout" in the line (and a hard exit after it has been printed), not in a lost run.
     hard_exit = False
-    if use_dist and route == "torch" and args.bcast == "torch":
+    if args.full and use_dist and route == "torch" and args.bcast == "torch":
         import threading
         from auralis_amd.parallel import broadcast_conditioning_native
         res = {}
@@ -899,20 +953,21 @@ def main():
             line["multi_gpu"] = multi
     if rank == 0:
         line["c2"], line["c5s"], line["c4"], line["c3f"] = c2, c5, c4, c3f
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(B.gpt_sd, B.xtts_sd, dims, B.cond, B.spk, B.text_ids, args.cpu_tokens, args.cpu_c1,
                                                 activation="gelu" if B.gelu_erf else "gelu_new")
         else:
             line["cpu_baseline"] = None
-        full_path = args.out
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
-            with open(full_path, "w") as f:
-                json.dump(line, f, indent=1)
-        except OSError as ex:
-            _log(f"could not write {full_path}: {ex}")
-            full_path = None
-        print("[bench full] " + json.dumps(line), file=sys.stderr, flush=True)
+        full_path = args.out if args.full else None
+        if full_path:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
+                with open(full_path, "w") as f:
+                    json.dump(line, f, indent=1)
+            except OSError as ex:
+                _log(f"could not write {full_path}: {ex}")
+                full_path = None
+            print("[bench full] " + json.dumps(line), file=sys.stderr, flush=True)
         comp = compact(line, os.path.relpath(full_path, ROOT) if full_path and os.path.isabs(full_path) else full_path)
         txt = json.dumps(comp, separators=(",", ":"))
         _log(f"compact line: {len(txt)} bytes")

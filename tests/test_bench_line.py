@@ -3,6 +3,8 @@
 import argparse
 import json
 
+import numpy as np
+
 import bench
 
 
@@ -79,3 +81,45 @@ def test_compact_line_is_small_and_complete():
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in back["cpu_baseline"], key
     assert "workload" in back["config"] and "model" not in back["config"]
+
+
+def test_plain_line_carries_the_contract_fields_without_the_full_run():
+    """A run without --full has no profile pass, side workloads or CPU baseline: the line still holds every contract field."""
+    line = {"metric": "audio_samples_per_s (64-way batch; rtf = wall_s / audio_s alongside)", "value": 36856512.3, "unit": "audio-samples/s",
+            "n_gpus": 1, "steps": 5, "warmup": 2, "ms_per_step": 541.8891, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32 (GPT; GEMMs as exact bf16x3 splits, f32 acc) + f16-in/f32-acc vocoder", "data": "synthetic", "rtf": 0.00065,
+            "config": {"workload": "BASELINE configs[2]", "gpt_layers": 30}, "kernels": None, "dominant_share": None,
+            "decode_step": bench.decode_step_roofline(_stats()),
+            "breakdown_ms_per_step": {"gpt": 480.0, "gpt_prefill": 25.0, "gpt_decode": 455.0, "vocoder": 61.0, "gpt_ms_per_decode_step": 1.61},
+            "c2": None, "c5s": None, "c4": None, "c3f": None, "cpu_baseline": None}
+    back = json.loads(json.dumps(bench.compact(line, None), separators=(",", ":")))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert back[key] == line[key] or abs(back[key] - line[key]) < 1e-3 * abs(line[key]), key
+    assert back["roofline"] is None and back["cpu_baseline"] is None and back["full_report"] is None
+
+
+def _outs(lengths, seed=0):
+    rng = np.random.default_rng(seed)
+    return [{"seq_id": 100 + b, "tokens": rng.integers(0, 1024, 7).astype(np.int32),
+             "wav": rng.standard_normal(n).astype(np.float32)} for b, n in enumerate(lengths)]
+
+
+def test_dump_outputs_whole_waveforms_when_they_fit(tmp_path):
+    outs = _outs([50, 50, 40])
+    bench.dump_outputs(str(tmp_path), outs)
+    tok, wav, pos = (np.load(tmp_path / f"{n}.npy") for n in ("tokens", "wav", "wav_positions"))
+    assert tok.dtype == np.float32 and wav.dtype == np.float32 and pos.dtype == np.float64
+    assert (tok == np.stack([o["tokens"] for o in outs])).all()
+    assert (pos == np.arange(50)).all() and wav.shape == (3, 50)
+    assert (wav[0] == outs[0]["wav"]).all() and (wav[2, :40] == outs[2]["wav"]).all() and (wav[2, 40:] == 0).all()
+
+
+def test_dump_outputs_samples_a_fixed_subset_of_large_waveforms(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_WAV_BYTES", 4 * 2 * 64)   # room for 64 positions of 2 rows
+    outs = _outs([1000, 1000])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    pos = np.load(tmp_path / "a" / "wav_positions.npy")
+    assert pos.shape == (64,) and (np.diff(pos) > 0).all() and (pos == np.load(tmp_path / "b" / "wav_positions.npy")).all()
+    wav = np.load(tmp_path / "a" / "wav.npy")
+    assert (wav == np.stack([o["wav"][pos.astype(np.int64)] for o in outs])).all()

@@ -6,7 +6,7 @@ exec < /dev/null
 TAG=${1:-a}
 mkdir -p gpurun_out
 for R in 1 2 3; do for T in 1 0; do
-  AUR_PREFILL_TAIL=$T python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-side --out /tmp/pt_$T.json > /dev/null 2>&1
+  AUR_PREFILL_TAIL=$T python bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-side --out /tmp/pt_$T.json > /dev/null 2>&1
   python - <<PY
 import json
 r = json.load(open("/tmp/pt_$T.json"))
