@@ -232,7 +232,6 @@ public:
         HIP_CHECK(hipMemsetAsync(ksp_cnt_.p, 0, (size_t)kGemmKspTiles * sizeof(unsigned), st_));
         h_block_tables_.assign((size_t)(S + 1) * kMaxBlocks, 0);
         spk_info_.assign(cfg_.max_speakers, SpeakerInfo{});
-        if (const char* e = getenv("AUR_SHARE_PREFIX")) share_prefix_ = atoi(e) != 0;
         slot_owner_.assign(S, nullptr);
         HIP_CHECK(hipStreamCreateWithPriority(&st2_, hipStreamDefault, prio_hi));
         HIP_CHECK(hipStreamCreateWithPriority(&st_voc_, hipStreamDefault, prio_lo));
@@ -248,7 +247,6 @@ public:
         if (const char* e = getenv("AUR_CONV_DMA")) conv_dma_ = atoi(e) != 0;   // 0: register-staged ResBlock convs (A/B only)
         if (const char* e = getenv("AUR_GEMM_PRESPLIT")) gemm_presplit_ = atoi(e) != 0; // 0: prompt-row GEMMs split their weights per tile instead of reading the planes packed at load time (A/B only)
         if (const char* e = getenv("AUR_DECODE_PIPELINE")) pipeline_ = atoi(e) != 0;
-        if (const char* e = getenv("AUR_WAV_DIRECT")) wav_direct_ = atoi(e) != 0;   // 0: conv_post writes device memory, one D2H copy per sequence behind it (A/B only)
         if (const char* e = getenv("AUR_SAMPLER_FULL_SORT")) sampler_full_sort_ = atoi(e) != 0;
         if (const char* e = getenv("AUR_HOST_TRACE")) host_trace_ = atoi(e) != 0;
         if (const char* e = getenv("AUR_TEST_FAIL_STEP")) fail_at_step_ = atoi(e);
@@ -524,7 +522,7 @@ public:
     void prefill_speaker_prefix(int row) {
         SpeakerInfo& si = spk_info_[row];
         si.ready = false;
-        if (!share_prefix_ || w_.find("gpt.wte") == w_.end()) return;   // GPT weights not loaded yet: unshared path
+        if (w_.find("gpt.wte") == w_.end()) return;   // GPT weights not loaded yet: unshared path
         ensure_gpt();
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -2059,17 +2057,20 @@ private:
         v_post_ = W("voc.conv_post.w");
         voc_ready_ = true;
     }
+    // the event pair of the next profiled conv launch (nullptr when the engine does not profile)
+    ConvEvent* next_conv_event() {
+        if (!cfg_.profile) return nullptr;
+        if (n_conv_events_ == conv_events_.size()) {
+            ConvEvent e{};
+            HIP_CHECK(hipEventCreate(&e.a));
+            HIP_CHECK(hipEventCreate(&e.b));
+            conv_events_.push_back(e);
+        }
+        return &conv_events_[n_conv_events_++];
+    }
     void conv(ConvArgs& a, int KS, int DIL, double tot_in, double tot_out) {
-        const bool prof = cfg_.profile != 0;
-        ConvEvent* ev = nullptr;
-        if (prof) {
-            if (n_conv_events_ == conv_events_.size()) {
-                ConvEvent e{};
-                HIP_CHECK(hipEventCreate(&e.a));
-                HIP_CHECK(hipEventCreate(&e.b));
-                conv_events_.push_back(e);
-            }
-            ev = &conv_events_[n_conv_events_++];
+        ConvEvent* ev = next_conv_event();
+        if (ev) {
             // class for the per-stage roofline: ResBlock convs by channel count (256 / 128 / 64 / 32 -> 0..3), everything
             // else (conv_pre, the four transposed convs) -> 4
             ev->kind = (a.ups_s == 0 && a.Cin == a.Cout) ? (a.Cout == 256 ? 0 : a.Cout == 128 ? 1 : a.Cout == 64 ? 2 : a.Cout == 32 ? 3 : 4) : 4;
@@ -2085,19 +2086,11 @@ private:
             launch_conv1d_f16(a, KS, DIL, st_voc_);
         else
             launch_conv1d(a, KS, DIL, st_voc_);
-        if (prof) HIP_CHECK(hipEventRecord(ev->b, st_voc_));
+        if (ev) HIP_CHECK(hipEventRecord(ev->b, st_voc_));
     }
     void round_conv(RoundArgs& a, int KS, int DIL, double tot) {
-        const bool prof = cfg_.profile != 0;
-        ConvEvent* ev = nullptr;
-        if (prof) {
-            if (n_conv_events_ == conv_events_.size()) {
-                ConvEvent e{};
-                HIP_CHECK(hipEventCreate(&e.a));
-                HIP_CHECK(hipEventCreate(&e.b));
-                conv_events_.push_back(e);
-            }
-            ev = &conv_events_[n_conv_events_++];
+        ConvEvent* ev = next_conv_event();
+        if (ev) {
             ev->kind = a.C == 64 ? 2 : 3;
             ev->flops = 2.0 * (2.0 * a.C * KS * a.C * tot);   // conv1 + conv2
             // stream in, then: stream out (mode 0) | running sum out (1) | in and out (2) | running sum in, stage output out (3)
@@ -2106,7 +2099,7 @@ private:
             HIP_CHECK(hipEventRecord(ev->a, st_voc_));
         }
         launch_resblock_round_f16(a, KS, DIL, st_voc_);
-        if (prof) HIP_CHECK(hipEventRecord(ev->b, st_voc_));
+        if (ev) HIP_CHECK(hipEventRecord(ev->b, st_voc_));
     }
     void collect_conv_events() {
         for (size_t i = 0; i < n_conv_events_; ++i) {
@@ -2281,7 +2274,6 @@ private:
             cond[b] = voc_batch_[b]->spk_row;
             voc_max_samples_ = std::max(voc_max_samples_, frames_for(voc_nl_[b]) * 256);
         }
-        if (!wav_direct_) tmp_wav_.ensure((size_t)B * voc_max_samples_ * 4);
         {
             std::lock_guard<std::mutex> lk(mu_);
             voc_block_ = nullptr;
@@ -2304,18 +2296,11 @@ private:
         // decode step being over).  hipHostMalloc memory is device-visible and coherent; the event below orders the host's reads.
         float* hw = voc_block_->buf.as<float>();
         float* hl = hw + (size_t)B * voc_max_samples_;
-        run_vocoder(B, voc_nl_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, wav_direct_ ? hw : tmp_wav_.as<float>(),
-                    voc_max_samples_);
-        for (int b = 0; b < B; ++b) {
-            const int ns = frames_for(voc_nl_[b]) * 256;
-            if (!wav_direct_)
-                HIP_CHECK(hipMemcpyAsync(hw + (size_t)b * voc_max_samples_, tmp_wav_.as<float>() + (long)b * voc_max_samples_,
-                                         (size_t)ns * 4, hipMemcpyDeviceToHost, st_voc_));
-            if (cfg_.return_latents)
-                HIP_CHECK(hipMemcpyAsync(hl + (size_t)b * kMaxLatRows * kHidden,
-                                         latpool_.as<float>() + (long)rows[b] * kMaxLatRows * kHidden,
-                                         (size_t)voc_nl_[b] * kHidden * 4, hipMemcpyDeviceToHost, st_voc_));
-        }
+        run_vocoder(B, voc_nl_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_);
+        for (int b = 0; b < B && cfg_.return_latents; ++b)
+            HIP_CHECK(hipMemcpyAsync(hl + (size_t)b * kMaxLatRows * kHidden,
+                                     latpool_.as<float>() + (long)rows[b] * kMaxLatRows * kHidden,
+                                     (size_t)voc_nl_[b] * kHidden * 4, hipMemcpyDeviceToHost, st_voc_));
         HIP_CHECK(hipEventRecord(ev_voc_done_, st_voc_));
         voc_active_ = true;
     }
@@ -2400,7 +2385,6 @@ private:
     };
     uint64_t spk_clock_ = 0;
     std::vector<SpeakerInfo> spk_info_;
-    bool share_prefix_ = true;        // AUR_SHARE_PREFIX=0 disables
     bool share_prefix_now_ = true;    // dbg_prefill turns it off to return every prompt row
     std::mutex gpu_mu_;
     std::unique_ptr<CondNet> cond_net_;
@@ -2463,7 +2447,6 @@ private:
     int admit_hold_steps_ = 0;
     static constexpr int kVocHoldSteps = 16;     // longest wait of a finished sequence for a fuller vocoder batch, in aur_steps (~30 ms)
     int voc_hold_steps_ = 0;
-    bool wav_direct_ = true;   // AUR_WAV_DIRECT
     std::vector<Seq*> slot_owner_;
     std::vector<Seq*> just_finished_;
     int64_t finished_total_ = 0;

@@ -685,28 +685,23 @@ __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)
 // NWV = waves per workgroup: the tile is MT channels x (NWV * 32 * WN) positions.  The packed weights of a chunk are the same for
 // every position tile, so a workgroup of 8 waves (512 positions) pulls them through the CU's L1 once for twice the MFMAs.
 // EPIH: the all-halves epilogue (conv_epilogue_plain_h; the launcher checks that the tensors are halves).
-// MT = 128 (round 6): the tile spans TWO of the packed 64-channel weight tiles (the packing stays [Mtot/64][Cin/16][KS][64][16]: the
-// chunk's two weight images land back to back in LDS), a wave keeps a 128-channel x 64-position accumulator tile (128 registers: one
-// workgroup of eight waves per CU), and every staged input window feeds twice the MFMAs: the global -> LDS operand fill, which bounds
-// the k = 3 / 7 convs of the 128- and 256-channel stages (~12.5 B/clk/CU measured, profiles/r05_pmc_conv_latency.txt), drops from
-// 22.6 to 14.4 KB per 96 MFMAs at k = 3.  Same chunk, tap and MFMA order per output element: bitwise the MT = 64 result.
+// MT, the output-channel tile, is 64: one packed weight tile ([Mtot/64][Cin/16][KS][64][16]).
 template <int KS, int DIL, int MT, int NBUF, int NWV = 4, bool EPIH = false>
-__global__ __launch_bounds__(64 * NWV, MT == 128 ? 2 : NWV == 4 ? 2 : 4) void conv1d_dma_f16_kernel(ConvArgs a) {   // (two workgroups per CU; one at MT = 128)
+__global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 4) void conv1d_dma_f16_kernel(ConvArgs a) {   // (two workgroups per CU)
+    static_assert(MT == 64, "64-channel tile");
     constexpr int CK = 16;
     constexpr int WM = MT / 32;
-    constexpr int WN = (MT == 32) ? 4 : 2;
+    constexpr int WN = 2;
     constexpr int NTW = 32 * WN;
     constexpr int NT = NWV * NTW;
     constexpr int HALO = (KS - 1) * DIL;
     constexpr int XROW = NT + HALO;
-    constexpr int MTP = MT == 128 ? 64 : MT;               // channels per packed weight tile
-    constexpr int WIP = KS * MTP * 2 / 64;                 // 1-KiB copies of one packed tile's chunk
-    constexpr int WI = WIP * (MT / MTP);                   // weight copies per chunk
+    constexpr int WI = KS * MT * 2 / 64;                   // weight copies (1 KiB each) per chunk
     constexpr int XI0 = (2 * XROW + 63) / 64;
     constexpr int XI = XI0 + (NWV - (WI + XI0) % NWV) % NWV;   // input-window copies, padded so that every wave issues IPW of them
     constexpr int IPW = (WI + XI) / NWV;
     constexpr int BUF = (WI + XI) * 1024;
-    static_assert((KS * MTP * 2) % 64 == 0 && IPW * (NBUF - 2) < 64, "DMA bookkeeping");
+    static_assert((KS * MT * 2) % 64 == 0 && IPW * (NBUF - 2) < 64, "DMA bookkeeping");
     static_assert(NBUF * BUF <= 160 * 1024, "LDS");
     __shared__ __attribute__((aligned(1024))) char smem[NBUF * BUF];
 
@@ -728,8 +723,8 @@ __global__ __launch_bounds__(64 * NWV, MT == 128 ? 2 : NWV == 4 ? 2 : 4) void co
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
 
-    const long wtile_bytes = (long)(a.Cin / CK) * (WIP * 1024);   // one packed 64- (32-) channel tile, all chunks
-    const char* wsrc_tile = reinterpret_cast<const char*>(a.wp16) + (long)mtile * (MT / MTP) * wtile_bytes;
+    const long wtile_bytes = (long)(a.Cin / CK) * (WI * 1024);   // one packed 64-channel tile, all chunks
+    const char* wsrc_tile = reinterpret_cast<const char*>(a.wp16) + (long)mtile * wtile_bytes;
     const _Float16* xhb = reinterpret_cast<const _Float16*>(a.x) + (long)b * a.x_bstride;
     const unsigned sbase = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem;
     const int nch = a.Cin / CK;
@@ -740,10 +735,9 @@ __global__ __launch_bounds__(64 * NWV, MT == 128 ? 2 : NWV == 4 ? 2 : 4) void co
         for (int k = 0; k < IPW; ++k) {
             const int ii = wvs + NWV * k;
             const bool is_w = ii < WI;   // wave-uniform; selects instead of branches keep the copy sequence straight-line
-            const int iw = (MT == MTP) ? ii : (ii >= WIP ? ii - WIP : ii);   // copy index inside its packed tile
-            const int s = (is_w ? iw : ii - WI) * 64 + lane, row = s >> 1, h = (s & 1) ^ ((row >> 3) & 1);
+            const int s = (is_w ? ii : ii - WI) * 64 + lane, row = s >> 1, h = (s & 1) ^ ((row >> 3) & 1);
             const int t = q0 - a.padl + row;
-            const char* wsrc = wsrc_tile + ((MT != MTP && ii >= WIP) ? wtile_bytes : 0L) + (long)c * (WIP * 1024) + (row * 2 + h) * 16;
+            const char* wsrc = wsrc_tile + (long)c * (WI * 1024) + (row * 2 + h) * 16;
             const char* xsrc = reinterpret_cast<const char*>(xhb + ((long)c * a.x_stride + t) * 16 + 8 * h);
             const char* src = is_w ? wsrc : (t >= 0 && t < len_in) ? xsrc : reinterpret_cast<const char*>(a.zeros);
             glds16(src, __builtin_amdgcn_readfirstlane(dst0 + (unsigned)ii * 1024));
@@ -771,8 +765,7 @@ __global__ __launch_bounds__(64 * NWV, MT == 128 ? 2 : NWV == 4 ? 2 : 4) void co
         for (int j = 0; j < KS; ++j) {
             h16x8 av[WM], bv[WN];
 #pragma unroll
-            for (int m = 0; m < WM; ++m)   // (MT = 128: m = 2, 3 live in the second packed tile's image, WIP KiB further on)
-                av[m] = *reinterpret_cast<const h16x8*>(wb + (m * 32 / MTP) * (WIP * 1024) + (j * MTP + (m * 32) % MTP) * 32);
+            for (int m = 0; m < WM; ++m) av[m] = *reinterpret_cast<const h16x8*>(wb + (j * MT + m * 32) * 32);
             const int i0 = l31 + j * DIL;
             const char* xp = xb + i0 * 32 + 16 * (hi ^ ((i0 >> 3) & 1));
 #pragma unroll
@@ -798,70 +791,36 @@ __global__ __launch_bounds__(64 * NWV, MT == 128 ? 2 : NWV == 4 ? 2 : 4) void co
     }
 }
 
-// Workgroup shape of the 64-channel-tile convs (the 256- and 128-channel stages): 8 = eight waves x 64 positions, two workgroups per
-// CU (default since round 5: the chunk's packed weights pass through the CU's L1 once per 512 positions instead of once per 256 --
+// Workgroup shape of the k >= 3 convs (the ResBlock convs of the 256- and 128-channel stages, conv_pre): eight waves x 64 positions, two
+// workgroups per CU (since round 5: the chunk's packed weights pass through the CU's L1 once per 512 positions instead of once per 256 --
 // PMC showed the L1 stalled on its pending-request limit 45-61 % of the time, profiles/r05_pmc_conv_latency.txt; 61.8 vs 65.4 ms per
-// 64 utterances); AUR_CONV_WAVES=4 selects round 4's 256-position tiles (A/B).  Also measured, not kept: one 1024-position workgroup
-// of 16 waves per CU 63.2 ms; four waves x 128 positions (256 registers, an A fragment serves four MFMAs) 64.8.
-static int conv_dma_waves() {
-    static const int w = [] {
-        const char* e = getenv("AUR_CONV_WAVES");
-        return e ? atoi(e) : 8;
-    }();
-    return w;
-}
-// Output-channel tile of the all-halves convs whose Mtot is a multiple of 128 (the ResBlock convs of the 256- and 128-channel
-// stages, conv_pre): 64 (default) or 128 (AUR_CONV_MT=128, A/B).  Bit mask AUR_CONV_MT128_KS selects the tap counts that take the
-// wide tile (1 = k 3, 2 = k 7, 4 = k 11; default all).  Measured in round 6 on one box, conv time per 64 utterances
+// 64 utterances against round 4's four waves x 64 positions, which the transposed convs keep).  Also measured, not kept: one
+// 1024-position workgroup of 16 waves per CU 63.2 ms; four waves x 128 positions (256 registers, an A fragment serves four MFMAs) 64.8.
+// A 128-output-channel tile (round 6: two packed weight tiles per chunk, a 128-channel x 64-position accumulator tile per wave, every
+// staged input window feeding twice the MFMAs; bitwise equal) measured on one box, conv time per 64 utterances
 // (profiles/r06_conv_mt_ab.log): 64-channel tile 64.2 / 64.0 ms; 128-channel tile for every k 66.0, for k = 3 only 65.2, k = 7 only
 // 64.9, k = 11 only 65.2 (256-channel class 0.41 -> 0.38 of the matrix peak, 128-channel class 0.345 -> 0.324).  The wide tile halves
 // the window bytes staged per MFMA and cuts the LDS fragment reads per MFMA from 1 to 0.75, and still loses: at 128 accumulator
 // registers a CU holds ONE workgroup of eight waves, and what the second workgroup of the 64-channel form hides -- the per-chunk
 // barrier and the wait for the chunk's copies -- is exposed.  The operand fill is therefore not what bounds these kernels; the
 // vocoder is closed at this tiling.
-static int conv_dma_mt() {
-    static const int v = [] {
-        const char* e = getenv("AUR_CONV_MT");
-        return e ? atoi(e) : 64;
-    }();
-    return v;
-}
-static int conv_dma_mt128_ks() {
-    static const int v = [] {
-        const char* e = getenv("AUR_CONV_MT128_KS");
-        return e ? atoi(e) : 7;
-    }();
-    return v;
-}
 template <int KS, int DIL>
 static void launch_conv_dma(const ConvArgs& a, hipStream_t st) {
-    constexpr int NBUF = KS >= 11 ? 2 : KS >= 3 ? 3 : 4;   // the fewer taps, the shorter a chunk's MFMA phase and the deeper the prefetch
-    AUR_REQUIRE(a.x_f16 && a.zeros && a.Cin % 16 == 0 && a.Cout % 16 == 0 && a.wp16, "conv dma: fp16 interleaved input, zero page");
+    constexpr int NBUF = KS == 2 ? 4 : KS >= 7 ? 2 : 3;   // the fewer taps, the shorter a chunk's MFMA phase and the deeper the prefetch
+    AUR_REQUIRE(a.x_f16 && a.zeros && a.Cin % 16 == 0 && a.Cout % 16 == 0 && a.wp16 && a.Mtot % 64 == 0,
+                "conv dma: fp16 interleaved input, zero page, 64-channel tiles");
     AUR_REQUIRE(a.Cin / 16 >= NBUF - 1, "conv dma: fewer input-channel chunks than the prefetch depth");
     trace_launch("conv1d_dma_f16_kernel");
     const int n_q = a.ups_s ? a.max_len + 1 : a.max_len;
-    const bool all_halves = a.ups_s == 0 && (!a.res || a.res_f16) && (a.mrf_mode == 0 || a.mrf_f16) &&
-                            ((a.mrf_mode == 1 || a.mrf_mode == 2) || a.out_act_f16);
-    if constexpr (KS >= 3) {
-        const int ksbit = KS == 3 ? 1 : KS == 7 ? 2 : 4;
-        if (a.Mtot % 128 == 0 && conv_dma_waves() == 8 && all_halves && conv_dma_mt() == 128 && (conv_dma_mt128_ks() & ksbit)) {
-            constexpr int NB128 = KS >= 7 ? 2 : 3;
-            dim3 grid((n_q + 511) / 512, a.Mtot / 128, a.B);
-            hipLaunchKernelGGL((conv1d_dma_f16_kernel<KS, DIL, 128, NB128, 8, true>), grid, dim3(512), 0, st, a);
-            return;
-        }
-    }
-    if (a.Mtot % 64 == 0 && conv_dma_waves() == 8 && KS >= 3 && all_halves) {
-        constexpr int NB8 = KS >= 7 ? 2 : 3;
-        dim3 grid((n_q + 511) / 512, a.Mtot / 64, a.B);
-        hipLaunchKernelGGL((conv1d_dma_f16_kernel<KS, DIL, 64, NB8, 8, true>), grid, dim3(512), 0, st, a);
-    } else if (a.Mtot % 64 == 0) {
+    if constexpr (KS == 2) {   // the transposed convs
         dim3 grid((n_q + 255) / 256, a.Mtot / 64, a.B);
         hipLaunchKernelGGL((conv1d_dma_f16_kernel<KS, DIL, 64, NBUF>), grid, dim3(256), 0, st, a);
     } else {
-        AUR_REQUIRE(a.Mtot % 32 == 0, "conv dma: Mtot % 32");
-        dim3 grid((n_q + 511) / 512, a.Mtot / 32, a.B);
-        hipLaunchKernelGGL((conv1d_dma_f16_kernel<KS, DIL, 32, NBUF>), grid, dim3(256), 0, st, a);
+        const bool all_halves = a.ups_s == 0 && (!a.res || a.res_f16) && (a.mrf_mode == 0 || a.mrf_f16) &&
+                                ((a.mrf_mode == 1 || a.mrf_mode == 2) || a.out_act_f16);
+        AUR_REQUIRE(all_halves, "conv dma: k >= 3 reads and writes fp16 interleaved tensors only");
+        dim3 grid((n_q + 511) / 512, a.Mtot / 64, a.B);
+        hipLaunchKernelGGL((conv1d_dma_f16_kernel<KS, DIL, 64, NBUF, 8, true>), grid, dim3(512), 0, st, a);
     }
 }
 
@@ -1048,20 +1007,24 @@ static void launch_round_c(const RoundArgs& a, hipStream_t st) {
     // global memory into registers, one chunk ahead, no weight buffers in LDS and two barriers per tile instead of one per chunk
     // (every wave of a channel group re-reads the same lines through the L1) 64.3 vs 61.0 (64-channel class 0.236 vs 0.265, 32-channel
     // 0.190 vs 0.216), bitwise equal.
-    if (a.C == 64 && KS < 11) {
-        constexpr int nt2 = 128 - (KS - 1);
-        hipLaunchKernelGGL((resblock_round_f16_kernel<KS, DIL, 64, 1, 128>), dim3((a.max_len + nt2 - 1) / nt2, a.B), dim3(512), 0, st, a);
-        return;
+    if (a.C == 64) {
+        if constexpr (KS < 11) {
+            constexpr int nt2 = 128 - (KS - 1);
+            hipLaunchKernelGGL((resblock_round_f16_kernel<KS, DIL, 64, 1, 128>), dim3((a.max_len + nt2 - 1) / nt2, a.B), dim3(512), 0, st, a);
+        } else {
+            constexpr int nt2 = 256 - (KS - 1);
+            hipLaunchKernelGGL((resblock_round_f16_kernel<KS, DIL, 64, 2, 256>), dim3((a.max_len + nt2 - 1) / nt2, a.B), dim3(512), 0, st, a);
+        }
+    } else if (a.C == 32) {
+        // (A persistent, weight-stationary form of the 32-channel round -- both convs' weights as A fragments in registers, a loader
+        // wave double- / triple-buffering the window by LDS-DMA, seven consumer waves, two barriers per tile -- measured SLOWER than
+        // this per-tile kernel in every variant: 10.6 ms per stage with one tile of lead, 11.2 with two, 10.2 with two workgroups
+        // per CU for k = 3 / 7, against 9.6; bit-identical results.  DESIGN section 7.)
+        constexpr int nt2 = 256 - (KS - 1);
+        hipLaunchKernelGGL((resblock_round_f16_kernel<KS, DIL, 32, 1, 256>), dim3((a.max_len + nt2 - 1) / nt2, a.B), dim3(512), 0, st, a);
+    } else {
+        throw InvalidArgument("resblock round: 64 or 32 channels");
     }
-    // (A persistent, weight-stationary form of the 32-channel round -- both convs' weights as A fragments in registers, a loader
-    // wave double- / triple-buffering the window by LDS-DMA, seven consumer waves, two barriers per tile -- measured SLOWER than
-    // this per-tile kernel in every variant: 10.6 ms per stage with one tile of lead, 11.2 with two, 10.2 with two workgroups
-    // per CU for k = 3 / 7, against 9.6; bit-identical results.  DESIGN section 7.)
-    constexpr int nt2 = 256 - (KS - 1);
-    const dim3 grid((a.max_len + nt2 - 1) / nt2, a.B);
-    if (a.C == 64) hipLaunchKernelGGL((resblock_round_f16_kernel<KS, DIL, 64, 2, 256>), grid, dim3(512), 0, st, a);
-    else if (a.C == 32) hipLaunchKernelGGL((resblock_round_f16_kernel<KS, DIL, 32, 1, 256>), grid, dim3(512), 0, st, a);
-    else throw InvalidArgument("resblock round: 64 or 32 channels");
 }
 
 void launch_resblock_round_f16(const RoundArgs& a, int KS, int DIL, hipStream_t st) {
