@@ -77,15 +77,20 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
     # ------------------------------------------------------------------ construction
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, max_concurrency: int = 10, device: int = 0,
-                        vocoder: str = "fp16", **kwargs) -> "XTTSv2Engine":
+                        vocoder: str = "fp16", gpt: str = "fp32", kv: str = "fp32", **kwargs) -> "XTTSv2Engine":
         """Load a checkpoint directory in the reference's on-disk format (checkpoint.py docstring).  kwargs the
         reference forwards to vLLM (tensor_parallel_size, pipeline_parallel_size, gpt_model, torch_dtype, device_map;
         XTTSv2.py:235-243) are accepted; tp/pp other than 1 are rejected (the path shards by utterance).
         `admit_min_batch` / `vocoder_min_batch` are the batcher's two grouping knobs, `max_speakers` the size of the engine's voice
-        table (include/auralis_amd.h, aur_config)."""
+        table (include/auralis_amd.h, aur_config).  gpt="fp16" keeps the four per-layer GPT linears as fp16 for the decode GEMMs
+        (aur_config.gpt_fp16: the exact model on effective weights, weights.gpt_fp16_effective), kv="fp16" the K/V pool
+        (aur_config.kv_fp16); "fp32" (default) is the exact contract for both."""
         from .._lib import NativeEngine
         from ..checkpoint import load_checkpoint, read_checkpoint_config
         from ..weights import pack_all
+        for knob, v in (("gpt", gpt), ("kv", kv)):
+            if v not in ("fp32", "fp16"):
+                raise ValueError(f"{knob}={v!r}: expected 'fp32' or 'fp16'")
         if kwargs.get("tensor_parallel_size", 1) != 1 or kwargs.get("pipeline_parallel_size", 1) != 1:
             raise ValueError("the MI355X path replicates the 0.4 B-parameter model per GPU; use one engine per GPU")
         gpt_sd, xtts_sd = load_checkpoint(pretrained_model_name_or_path)
@@ -97,7 +102,8 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
         native = NativeEngine(n_layer=ck.n_layer, max_seqs=max(1, max_concurrency), device=device,
                               vocoder_fp16=(vocoder == "fp16"), return_latents=False, gelu_erf=ck.gelu_erf,
                               admit_min_batch=int(kwargs.get("admit_min_batch", 0)), vocoder_min_batch=int(kwargs.get("vocoder_min_batch", 0)),
-                              max_speakers=int(kwargs.get("max_speakers", 0)), urgent_rows=int(kwargs.get("urgent_rows", 0)))
+                              max_speakers=int(kwargs.get("max_speakers", 0)), urgent_rows=int(kwargs.get("urgent_rows", 0)),
+                              gpt_fp16=(gpt == "fp16"), kv_fp16=(kv == "fp16"))
         native.load_weights(pack_all(gpt_sd, xtts_sd))
         if any(k.startswith("conditioning_encoder.") for k in xtts_sd):
             from ..weights import pack_conditioning

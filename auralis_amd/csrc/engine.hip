@@ -92,6 +92,8 @@ struct PinBlock {
 struct Tensor {
     std::unique_ptr<DevBuf> buf;
     int64_t numel = 0;
+    bool f16_eff = false;   // aur_config.gpt_fp16: the buffer holds the effective weights W'' (a per-layer matrix), or the LayerNorm
+                            // gain they were derived with, since the last load of this tensor
     float* d() const { return buf->as<float>(); }
 };
 
@@ -209,6 +211,9 @@ public:
                                       std::to_string((cap - 2L * cfg_.max_speakers) / kMaxBlocks) + " (asked for " + std::to_string(S) + ")");
         }
         gemm_prec_ = cfg_.gemm_f32_exact ? 0 : 1;
+        gpt_f16_ = cfg_.gpt_fp16 != 0;
+        AUR_REQUIRE(!(gpt_f16_ && cfg_.gemm_f32_exact), "gpt_fp16 and gemm_f32_exact exclude each other (the fp16-weight decode GEMMs "
+                                                        "run on the split arithmetic)");
         kv_.ensure((size_t)cfg_.n_layer * kv_layer_stride_ * (kv_half_ ? 2 : 4));
         for (int b = (int)n_blocks_ - 1; b >= 0; --b) free_blocks_.push_back(b);
         auto ints = [&](DevBuf& b, size_t n) {
@@ -298,10 +303,41 @@ public:
             if (!dst.buf) dst.buf.reset(new DevBuf());
             dst.buf->ensure((size_t)t[i].numel * sizeof(float));
             dst.numel = t[i].numel;
+            dst.f16_eff = false;
             HIP_CHECK(hipMemcpy(dst.buf->p, t[i].data, (size_t)t[i].numel * sizeof(float), hipMemcpyHostToDevice));
         }
         voc_ready_ = false;
         gpt_ready_ = false;
+        if (gpt_f16_) check_gpt_f16();
+    }
+    // aur_config.gpt_fp16: once every per-layer matrix and its LayerNorm gain are loaded, a matrix the rule rejects (not finite, or
+    // beyond the fp16 range after folding) fails the load that completed the set, before anything is converted
+    // the four per-layer matrices of layer prefix p, with the LayerNorm gain folded into each (empty: none)
+    struct F16Mat {
+        std::string w, gamma;
+        int K, N;
+    };
+    static std::vector<F16Mat> gpt_f16_mats(const std::string& p) {
+        return {{p + "attn.c_attn.w", p + "ln_1.w", kHidden, 3 * kHidden}, {p + "attn.c_proj.w", "", kHidden, kHidden},
+                {p + "mlp.c_fc.w", p + "ln_2.w", kHidden, 4 * kHidden}, {p + "mlp.c_proj.w", "", 4 * kHidden, kHidden}};
+    }
+    void check_gpt_f16() {
+        auto has = [&](const std::string& n, int64_t numel) { auto it = w_.find(n); return it != w_.end() && it->second.numel == numel; };
+        std::vector<F16Mat> mats;
+        for (int i = 0; i < cfg_.n_layer; ++i)
+            for (auto& m : gpt_f16_mats("gpt.h." + std::to_string(i) + "."))
+                if (!has(m.w, (int64_t)m.K * m.N) || (!m.gamma.empty() && !has(m.gamma, m.K))) return;   // not complete yet (or misshapen:
+                else mats.push_back(m);                                                                   // ensure_gpt reports that)
+        DevBuf dbad, scratch;
+        dbad.ensure(sizeof(int));
+        scratch.ensure((size_t)4 * kHidden * kHidden * 2);
+        HIP_CHECK(hipMemsetAsync(dbad.p, 0, sizeof(int), st_));
+        for (auto& m : mats)
+            launch_pack_wt16_f16(W(m.w), m.N, m.gamma.empty() ? nullptr : W(m.gamma), nullptr, scratch.p, dbad.as<int>(), m.K, m.N, st_);
+        int bad = 0;
+        HIP_CHECK(hipMemcpyAsync(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipStreamSynchronize(st_));
+        if (bad) throw InvalidArgument("gpt_fp16: a per-layer GPT linear is not finite or leaves the fp16 range after LayerNorm folding");
     }
     const float* W(const std::string& name, int64_t numel = -1) const {
         auto it = w_.find(name);
@@ -1018,8 +1054,29 @@ public:
             HIP_CHECK(hipMemcpy(dbe.p, beta, (size_t)K * 4, hipMemcpyHostToDevice));
         }
         GemmRowsArgs a{};
-        DevBuf dsc, dvec;
-        if (ln) {   // LayerNorm folded into the weights, as ensure_gpt() does at load time
+        DevBuf dsc, dvec, dbad;
+        if (gpt_f16_) {   // aur_config.gpt_fp16: the fp16 decode copy, as ensure_gpt() makes it for the four per-layer GEMMs
+            dbad.ensure(sizeof(int));
+            HIP_CHECK(hipMemsetAsync(dbad.p, 0, sizeof(int), st_));
+            if (ln) {
+                dvec.ensure((size_t)2 * N * 4);
+                launch_fold_ln_f16(dw.as<float>(), N, dg.as<float>(), dbe.as<float>(), bias ? db.as<float>() : nullptr, nullptr, dwt.p,
+                                   dvec.as<float>(), dvec.as<float>() + N, dbad.as<int>(), K, N, st_);
+                a.ln_c1 = dvec.as<float>();
+                a.bias = dvec.as<float>() + N;
+            } else {
+                launch_pack_wt16_f16(dw.as<float>(), N, nullptr, nullptr, dwt.p, dbad.as<int>(), K, N, st_);
+                if (!bias) {   // the kernel loads its bias unconditionally
+                    db.ensure((size_t)N * 4);
+                    HIP_CHECK(hipMemsetAsync(db.p, 0, (size_t)N * 4, st_));
+                }
+                a.bias = db.as<float>();
+            }
+            int bad = 0;
+            HIP_CHECK(hipMemcpyAsync(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+            HIP_CHECK(hipStreamSynchronize(st_));
+            AUR_REQUIRE(!bad, "dbg_gemm_rows: gpt_fp16 rejects these weights (not finite, or beyond the fp16 range after folding)");
+        } else if (ln) {   // LayerNorm folded into the weights, as ensure_gpt() does at load time
             dsc.ensure((size_t)K * N * 4);
             dvec.ensure((size_t)2 * N * 4);
             launch_fold_ln(dw.as<float>(), N, dg.as<float>(), dbe.as<float>(), bias ? db.as<float>() : nullptr, dsc.as<float>(),
@@ -1035,7 +1092,7 @@ public:
             a.bias = db.as<float>();
         }
         a.X = dx.as<float>(); a.xmt = mtt; a.Wt = dwt.as<float>(); a.M = M; a.N = N; a.K = K;
-        a.eps = 1e-5f; a.prec = gemm_prec_;
+        a.eps = 1e-5f; a.prec = gpt_f16_ ? 2 : gemm_prec_;
         if ((long)((M + 15) / 16) * (N / 16) <= kGemmKspTiles) { a.ksp_buf = ksp_buf_.as<float>(); a.ksp_cnt = ksp_cnt_.as<unsigned>(); }
         a.stats_in = ln ? dst.as<float2>() : nullptr;
         a.out = dout.as<float>(); a.ldo = N; a.omt = mtt;
@@ -1087,9 +1144,16 @@ public:
         HIP_CHECK(hipMemcpy(db.p, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dh0.p, hh.data(), hh.size() * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemsetAsync(dcnt.p, 0, 8, st_));
-        launch_pack_wt16(dw.as<float>(), N, dwt.as<float>(), K, N, st_);
+        if (gpt_f16_) {   // aur_config.gpt_fp16: the fp16 decode copy and arithmetic of the per-layer GEMMs
+            DevBuf dbad;
+            dbad.ensure(sizeof(int));
+            launch_pack_wt16_f16(dw.as<float>(), N, nullptr, nullptr, dwt.p, dbad.as<int>(), K, N, st_);
+            HIP_CHECK(hipStreamSynchronize(st_));
+        } else {
+            launch_pack_wt16(dw.as<float>(), N, dwt.as<float>(), K, N, st_);
+        }
         GemmRowsArgs a{};
-        a.xmt = mtt; a.omt = mtt; a.Wt = dwt.as<float>(); a.M = M; a.N = N; a.K = K; a.bias = db.as<float>(); a.prec = gemm_prec_;
+        a.xmt = mtt; a.omt = mtt; a.Wt = dwt.as<float>(); a.M = M; a.N = N; a.K = K; a.bias = db.as<float>(); a.prec = gpt_f16_ ? 2 : gemm_prec_;
         // references: no scratch -> the UNSPLIT kernel, one per operand set
         HIP_CHECK(hipMemcpyAsync(dref.p, dh0.p, hh.size() * 4, hipMemcpyDeviceToDevice, st_));
         for (int s = 0; s < 2; ++s) {
@@ -1411,6 +1475,26 @@ private:
         *c2 = v.as<float>() + N;
         return b.as<float>();
     }
+    // aur_config.gpt_fp16: the fp16 packed copy (launch_pack_wt16_f16, or launch_fold_ln_f16 with its epilogue vectors when gamma is
+    // given) of the loaded matrix `name`, which is overwritten with its effective weights W''
+    const float* f16_copy(const std::string& name, const float* gamma, const float* beta, const float* bias, int K, int N,
+                          const float** c1, const float** c2, int* bad) {
+        float* Wm = w_.at(name).d();
+        packed_.emplace_back(new DevBuf());
+        DevBuf& b = *packed_.back();
+        b.ensure((size_t)K * N * 2);
+        if (gamma) {
+            packed_.emplace_back(new DevBuf());
+            DevBuf& v = *packed_.back();
+            v.ensure((size_t)2 * N * sizeof(float));
+            launch_fold_ln_f16(Wm, N, gamma, beta, bias, Wm, b.p, v.as<float>(), v.as<float>() + N, bad, K, N, st_);
+            *c1 = v.as<float>();
+            *c2 = v.as<float>() + N;
+        } else {
+            launch_pack_wt16_f16(Wm, N, nullptr, Wm, b.p, bad, K, N, st_);
+        }
+        return b.as<float>();
+    }
     void ensure_gpt() {
         if (gpt_ready_) return;
         layers_.clear();
@@ -1430,12 +1514,38 @@ private:
             layers_.push_back(l);
         }
         packed_.clear();
+        if (gpt_f16_) {
+            // fp16 decode copies by the rule of aur_config.gpt_fp16; the matrices themselves are replaced by W'' in place, so the
+            // prompt-row GEMMs below (and second_pass) run on the same effective weights.  Converting W'' again gives the same bits.
+            check_gpt_f16();
+            DevBuf dbad;
+            dbad.ensure(sizeof(int));
+            for (int i = 0; i < cfg_.n_layer; ++i) {
+                LayerW& l = layers_[i];
+                const std::string p = "gpt.h." + std::to_string(i) + ".";
+                for (auto& m : gpt_f16_mats(p))
+                    if (!m.gamma.empty() && w_.at(m.w).f16_eff && !w_.at(m.gamma).f16_eff)
+                        throw StateError("gpt_fp16: " + m.gamma + " was loaded again after " + m.w + " was converted with the previous "
+                                         "one; load " + m.w + " again as well");
+                l.tqkv = f16_copy(p + "attn.c_attn.w", l.ln1w, l.ln1b, l.bqkv, H, 3 * H, &l.qkv_c1, &l.qkv_c2, dbad.as<int>());
+                l.tproj = f16_copy(p + "attn.c_proj.w", nullptr, nullptr, nullptr, H, H, nullptr, nullptr, dbad.as<int>());
+                l.tfc = f16_copy(p + "mlp.c_fc.w", l.ln2w, l.ln2b, l.bfc, H, 4 * H, &l.fc_c1, &l.fc_c2, dbad.as<int>());
+                l.tproj2 = f16_copy(p + "mlp.c_proj.w", nullptr, nullptr, nullptr, 4 * H, H, nullptr, nullptr, dbad.as<int>());
+                for (auto& m : gpt_f16_mats(p)) {
+                    w_.at(m.w).f16_eff = true;
+                    if (!m.gamma.empty()) w_.at(m.gamma).f16_eff = true;
+                }
+            }
+            HIP_CHECK(hipStreamSynchronize(st_));   // (dbad: checked before the conversion by check_gpt_f16)
+        }
         {
             for (auto& l : layers_) {
-                l.tqkv = folded_copy(l.wqkv, l.ln1w, l.ln1b, l.bqkv, H, 3 * H, &l.qkv_c1, &l.qkv_c2);
-                l.tproj = packed_copy(l.wproj, H, H, H);
-                l.tfc = folded_copy(l.wfc, l.ln2w, l.ln2b, l.bfc, H, 4 * H, &l.fc_c1, &l.fc_c2);
-                l.tproj2 = packed_copy(l.wproj2, H, 4 * H, H);
+                if (!gpt_f16_) {
+                    l.tqkv = folded_copy(l.wqkv, l.ln1w, l.ln1b, l.bqkv, H, 3 * H, &l.qkv_c1, &l.qkv_c2);
+                    l.tproj = packed_copy(l.wproj, H, H, H);
+                    l.tfc = folded_copy(l.wfc, l.ln2w, l.ln2b, l.bfc, H, 4 * H, &l.fc_c1, &l.fc_c2);
+                    l.tproj2 = packed_copy(l.wproj2, H, 4 * H, H);
+                }
                 l.sqkv = split_copy(l.wqkv, H, 3 * H);
                 l.sproj = split_copy(l.wproj, H, H);
                 l.sfc = split_copy(l.wfc, H, 4 * H);
@@ -1502,7 +1612,7 @@ private:
         return ev;
     }
     static double gemm_alg_bytes(const GemmRowsArgs& a, GemmRowsEpi epi) {
-        return 4.0 * ((double)a.K * a.N + (double)a.M * a.K + (double)a.M * a.N * (epi == kEpiResidual ? 2.0 : 1.0));
+        return (a.prec == 2 ? 2.0 : 4.0) * a.K * a.N + 4.0 * ((double)a.M * a.K + (double)a.M * a.N * (epi == kEpiResidual ? 2.0 : 1.0));
     }
     // the four GEMM launches of layer l exactly as forward_decode issues them; `redirect` sends every output to the profile scratch
     GemmRowsArgs decode_gemm_args(RowWs& w, int l, int kind, int M, const int* d_row_slot, bool redirect) {
@@ -1510,7 +1620,7 @@ private:
         const int mtt = w.rows_cap / 16;   // h, att, act are packed rows (pk_off) with this many 16-row tiles
         float* h = w.h.as<float>();
         GemmRowsArgs a{};
-        a.M = M; a.prec = gemm_prec_; a.xmt = mtt;
+        a.M = M; a.prec = gpt_f16_ ? 2 : gemm_prec_; a.xmt = mtt;
         a.ksp_buf = ksp_buf_.as<float>(); a.ksp_cnt = ksp_cnt_.as<unsigned>();
         if (kind == 0) {
             a.eps = 1e-5f; a.X = h; a.Wt = L.tqkv; a.N = 3 * kHidden; a.K = kHidden; a.bias = L.qkv_c2;
@@ -1962,7 +2072,7 @@ private:
             step_kv_tokens_ += (double)(sq->n_prompt + (int)sq->tokens.size() + (infl_.on ? 1 : 0));
         }
         stats_.decode_kv_bytes += (kv_half_ ? 4.0 : 8.0) * kHidden * step_kv_tokens_ * cfg_.n_layer;
-        stats_.decode_weight_bytes += 4.0 * ((double)cfg_.n_layer * 12.0 * kHidden * kHidden + (double)kHidden * kMelVocab);
+        stats_.decode_weight_bytes += (gpt_f16_ ? 2.0 : 4.0) * cfg_.n_layer * 12.0 * kHidden * kHidden + 4.0 * kHidden * kMelVocab;
         HIP_CHECK(hipEventRecord(ev_ds_[f.buf], st_));
         decode_kernels(w, M);
         HIP_CHECK(hipEventRecord(ev_de_[f.buf], st_));
@@ -2358,6 +2468,7 @@ private:
     std::vector<std::unique_ptr<DevBuf>> packed_;   // pack_wt16 copies (decode GEMM layout)
     DevBuf fold_scratch_;                           // load-time scratch of launch_fold_ln
     int gemm_prec_ = 1;                             // GemmRowsArgs.prec of every decode GEMM (aur_config.gemm_f32_exact)
+    bool gpt_f16_ = false;                          // aur_config.gpt_fp16: the four per-layer decode GEMMs run with prec 2 on fp16 copies
     const float* thead_ = nullptr;
     int fail_at_step_ = 0;              // AUR_TEST_FAIL_STEP=n: throw inside the n-th aur_step (recovery test)
     int fail_at_voc_ = 0;               // AUR_TEST_FAIL_VOC=n: throw inside the n-th vocoder launch, after the batch left the queue

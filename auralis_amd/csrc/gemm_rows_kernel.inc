@@ -58,7 +58,9 @@ void AUR_GR_NAME(const float* __restrict__ Wt_, const float* X_, const float* bi
     // groups landed on four XCDs and pulled the weights from HBM four times: PMC 18.7 MB per launch for 4.5 MB of weights)
     if (ntile >= n_tiles) return;
     const int n0 = ntile * 16 * NTL, m0 = mgrp * 16 * MT;
-    constexpr long wt_tile = (long)(K >> 4) * 64;   // float4s of one packed 16-column tile
+    // 16-byte pieces of one packed 16-column tile: a float4 per lane and K block (pack_wt16), or for PREC 2 eight fp16 per lane and
+    // K-block pair (pack_wt16_f16: the same 8 values the PREC 1 split takes from the float4s of blocks 2p, 2p + 1)
+    constexpr long wt_tile = PREC == 2 ? (long)(K >> 5) * 64 : (long)(K >> 4) * 64;
     const f32x4* wt = reinterpret_cast<const f32x4*>(Wt_) + (long)ntile * NTL * wt_tile + lane;
     // packed rows: the float4 of lane `lane` for (16-row tile t, K block kb) is at ((kb * xmt + t) * 64 + lane); rows >= M of
     // the last tiles are allocated but undefined: their products stay in their own (never stored) output rows
@@ -66,17 +68,23 @@ void AUR_GR_NAME(const float* __restrict__ Wt_, const float* X_, const float* bi
     // K = 4096: two chunk buffers (the loads run one 1024-deep chunk ahead of the MFMAs).  Three buffers measured slower
     // (13.6 vs 12.3 us at M = 64).
     constexpr int NBUF = (KCH > 1) ? 2 : 1;
-    f32x4 bf[NBUF][NTL][NB], af[NBUF][MT][NB];
-    // loads in K-block order (for PREC 1 in pairs of blocks): the MFMAs of block b need exactly the first (b + 1) / NB of the
-    // chunk's loads, and loads return in order
+    static_assert(PREC >= 0 && PREC <= 2 && NB % 2 == 0, "arithmetic; PREC 1 / 2 take K blocks in pairs");
+    constexpr int NBW = PREC == 2 ? NB / 2 : NB;   // weight pieces per wave and chunk
+    f32x4 bf[NBUF][NTL][NBW], af[NBUF][MT][NB];
+    // loads in K-block order (for PREC 1 and 2 in pairs of blocks; PREC 2: the pair's weight piece with the first block): the MFMAs
+    // of block b need exactly the first (b + 1) / NB of the chunk's loads, and loads return in order
     auto load_chunk = [&](int c, int buf) {
         const int kb0 = c * 64 + NB * wg;
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
+            if (PREC != 2 || !(b & 1)) {
+                const int bw = PREC == 2 ? b >> 1 : b;
+                const long off = PREC == 2 ? (long)((kb0 + b) >> 1) * 64 : (long)(kb0 + b) * 64;
 #pragma unroll
-            for (int t = 0; t < NTL; ++t) {
-                if constexpr (NT) bf[buf][t][b] = __builtin_nontemporal_load(&wt[t * wt_tile + (long)(kb0 + b) * 64]);
-                else bf[buf][t][b] = wt[t * wt_tile + (long)(kb0 + b) * 64];
+                for (int t = 0; t < NTL; ++t) {
+                    if constexpr (NT) bf[buf][t][bw] = __builtin_nontemporal_load(&wt[t * wt_tile + off]);
+                    else bf[buf][t][bw] = wt[t * wt_tile + off];
+                }
             }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) af[buf][mt][b] = xp[((long)(kb0 + b) * xmt + mt) * 64];
@@ -180,6 +188,23 @@ void AUR_GR_NAME(const float* __restrict__ Wt_, const float* X_, const float* bi
 #pragma unroll
                             for (int mt = 0; mt < MT; ++mt)
                                 acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[cur][mt][b][s], bf[cur][t][b][s], acc[mt][t], 0, 0, 0);
+                } else if constexpr (PREC == 2) {
+                    bf16x8 ah[MT], am[MT], al[MT];
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) split3_bf16(af[cur][mt][b], af[cur][mt][b + 1], ah[mt], am[mt], al[mt]);
+#pragma unroll
+                    for (int t = 0; t < NTL; ++t) {
+                        bf16x8 wh, wl;
+                        split2_f16(bf[cur][t][b >> 1], wh, wl);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) {
+                            lo[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[mt], wl, lo[mt][t], 0, 0, 0);
+                            lo[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], wh, lo[mt][t], 0, 0, 0);
+                            lo[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], wl, lo[mt][t], 0, 0, 0);
+                            lo[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[mt], wh, lo[mt][t], 0, 0, 0);
+                            acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], wh, acc[mt][t], 0, 0, 0);
+                        }
+                    }
                 } else {
                     bf16x8 ah[MT], am[MT], al[MT];
 #pragma unroll
@@ -368,16 +393,20 @@ void AUR_GR_LAUNCH(const GemmRowsArgs& a, bool ln, GemmRowsEpi epi, hipStream_t 
     AUR_REQUIRE(epi != kEpiQkv || (a.row_meta && a.kv_layer), "gemm_rows: the QKV epilogue needs the step's row_meta table and the K/V pool");
     GemmRowsShape s = gemm_rows_shape(a.M, a.N, a.K, ln);
     trace_launch("gemm_rows_kernel");
-    AUR_REQUIRE(a.prec == 0 || a.prec == 1, "gemm_rows: prec is 0 (exact f32 MFMA) or 1 (bf16 x 3 split)");
+    AUR_REQUIRE(a.prec >= 0 && a.prec <= 2, "gemm_rows: prec is 0 (exact f32 MFMA), 1 (bf16 x 3 split) or 2 (fp16 weights)");
     if (s.ksp > 1 && !(a.ksp_buf && a.ksp_cnt)) s = GemmRowsShape{1, 16, 1, a.M <= 16, 1};   // no scratch given: the unsplit kernel (same bits)
     if (s.ksp > 1) {
         AUR_REQUIRE((long)((a.M + 15) / 16) * (a.N / 16) <= kGemmKspTiles, "gemm_rows K split: more output tiles than the scratch holds");
-        if (a.prec == 1) D::template ksp<1>(a, epi, st);
+        if (a.prec == 2) D::template ksp<2>(a, epi, st);
+        else if (a.prec == 1) D::template ksp<1>(a, epi, st);
         else D::template ksp<0>(a, epi, st);
         HIP_CHECK(hipGetLastError());
         return;
     }
-    if (a.prec == 1) {
+    if (a.prec == 2) {
+        if (s.nt) D::template prec<2, true>(a, ln, epi, s, st);
+        else D::template prec<2, false>(a, ln, epi, s, st);
+    } else if (a.prec == 1) {
         if (s.nt) D::template prec<1, true>(a, ln, epi, s, st);
         else D::template prec<1, false>(a, ln, epi, s, st);
     } else {

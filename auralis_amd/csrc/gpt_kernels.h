@@ -50,7 +50,7 @@ enum GemmRowsEpi { kEpiBias = 0, kEpiBiasGelu = 1, kEpiResidual = 2, kEpiQkv = 3
 struct GemmRowsArgs {
     const float* X;      // packed rows, K columns
     int xmt;             // 16-row tiles allocated in X (pk_off's mtt); >= ceil(M / 64) * 4
-    const float* Wt;     // packed (pack_wt16)
+    const float* Wt;     // packed (pack_wt16); prec 2: the fp16 words of launch_pack_wt16_f16
     int M, N, K;
     const float* bias;   // [N], required (zeros for none); LayerNorm-folded GEMMs: c2 of launch_fold_ln
     const float* ln_c1;  // LayerNorm-folded GEMMs (ln != 0, K == 1024): c1 of launch_fold_ln, Wt = its folded packed weights
@@ -74,6 +74,9 @@ struct GemmRowsArgs {
     int prec;            // arithmetic: 0 = exact f32 MFMA (v_mfma_f32_16x16x4_f32); 1 = every operand split exactly into three bf16
                          // terms, six bf16 MFMAs per product with fp32 accumulation (same accuracy class as an fp32 dot product,
                          // not bitwise an fma chain; 2.7x less matrix-pipe time).  aur_config.gemm_f32_exact selects 0.
+                         // 2 = fp16 weights (Wt packed by launch_pack_wt16_f16, half the bytes): each fp16 weight splits exactly
+                         // into two bf16 terms, the activations into three as for 1, five bf16 MFMAs per product (the dropped
+                         // al * wl term is below 2^-24 of it).  aur_config.gpt_fp16 selects it for the four per-layer GEMMs.
     // K split over kGemmKsp workgroups per output tile (the K = 4096 projection at M <= 16 rows, where one workgroup per tile
     // leaves 3/4 of the CUs idle): every workgroup runs 16 / kGemmKsp of the 16 K-slices (each slice = the MFMA chain of one wave
     // of the unsplit kernel, bit for bit), publishes its per-wave partial tiles in ksp_buf, takes a ticket on ksp_cnt[tile], and
@@ -114,6 +117,17 @@ void launch_pack_wt16(const float* W, int ldw, float* Wt, int K, int N, hipStrea
 // epilogue, so nothing in front of its MFMAs depends on them.
 void launch_fold_ln(const float* W, int ldw, const float* gamma, const float* beta, const float* bias, float* scratch, float* Wt,
                     float* c1, float* c2, int K, int N, hipStream_t st);
+// fp16-weight form (aur_config.gpt_fp16; GemmRowsArgs::prec 2).  Per element, with g = gamma[k] (g = 1 and no fold when gamma is
+// null):  f = fp16_rne(fp32(g * W[k][n])),  W''[k][n] = fp32(f / g)  (fp16_rne(W[k][n]) where g == 0; = f without gamma).
+// Wt16 = f packed as [N/16][K/32][64 lanes][8 halves]: lane 16 q + j, half 4 h + s = f[32 p + 16 h + 4 q + s][16 nt + j], i.e. the
+// 8 values a lane of the PREC 1 kernel takes from the float4s of K blocks 2p, 2p + 1 -- one 16-byte load, one 1 KiB request per wave
+// per 16 x 32 block.  Weff (may alias W, ld = ldw) receives W''.  *bad is set to 1 when some W or f is not finite (f beyond the fp16
+// range rounds to infinity).  The fp32 input is read before anything is written, elementwise, so Weff == W converts in place.
+void launch_pack_wt16_f16(const float* W, int ldw, const float* gamma, float* Weff, void* Wt16, int* bad, int K, int N, hipStream_t st);
+// the LayerNorm-folded fp16 pair: c1[n] = sum_k f[k][n], c2[n] = sum_k beta[k] W''[k][n] + bias[n] (sums in double) from the
+// UNCONVERTED W, then launch_pack_wt16_f16 with gamma (W'' may be written over W)
+void launch_fold_ln_f16(const float* W, int ldw, const float* gamma, const float* beta, const float* bias, float* Weff, void* Wt16,
+                        float* c1, float* c2, int* bad, int K, int N, hipStream_t st);
 // decode tail: y[j] = final_norm(ln_f(h[j])) -> ybuf;  latents[slot][ngen[slot]] = final_norm(y[j]);  h and ybuf are
 // packed rows with `mtt` 16-row tiles, latents row-major
 void launch_final_rows(const float* h, int mtt, const int* sample_slot, const float* lnf_w, const float* lnf_b, const float* fn_w,

@@ -157,6 +157,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tile_kernel(const float* __restri
 // four coalesced dword loads k .. k+3 of one column.
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void split3_bf16x4(const f32x4& x, bf16x4& h, bf16x4& m, bf16x4& l) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -505,6 +506,95 @@ void launch_pack_wt16(const float* W, int ldw, float* Wt, int K, int N, hipStrea
     HIP_CHECK(hipGetLastError());
 }
 
+// ---- fp16 weights (aur_config.gpt_fp16, gpt_kernels.h launch_pack_wt16_f16): the rule of one element, shared by the c1 / c2 sums
+// and the packing so that both see the same f and W''.  Returns false for a weight the mode rejects.
+__device__ __forceinline__ bool f16_rule(float w, const float* gamma, int k, float& f, float& weff) {
+    if (!gamma) {
+        f = (float)(_Float16)w;
+        weff = f;
+    } else {
+        const float g = gamma[k];
+        float p = g * w;
+        // the fp32 product is rounded first (the rule, and its host mirror): without the barrier hipcc fuses the multiply and the
+        // fp16 conversion into one v_fma_mixlo_f16, a single rounding of the exact product
+        asm volatile("" : "+v"(p));
+        f = (float)(_Float16)p;
+        weff = g != 0.f ? __fdiv_rn(f, g) : (float)(_Float16)w;
+    }
+    return isfinite(w) && isfinite(f) && isfinite(weff);
+}
+__global__ __launch_bounds__(256) void pack_wt16_f16_kernel(const float* W, int ldw, const float* __restrict__ gamma, float* Weff,
+                                                            _Float16* __restrict__ Wt16, int* __restrict__ bad, int K, int N) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;   // one 8-half group of Wt16 (one lane of one 16 x 32 block)
+    const long total = (long)(N >> 4) * (K >> 5) * 64;
+    if (idx >= total) return;
+    const int lane = (int)(idx & 63);
+    const long blk = idx >> 6;
+    const int p = (int)(blk % (K >> 5)), nt = (int)(blk / (K >> 5));
+    const int j = lane & 15, q = lane >> 4;
+    const int n = 16 * nt + j;
+    float wv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) wv[i] = W[(long)(32 * p + 16 * (i >> 2) + 4 * q + (i & 3)) * ldw + n];
+    f16x8 o;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int k = 32 * p + 16 * (i >> 2) + 4 * q + (i & 3);
+        float f, we;
+        ok = f16_rule(wv[i], gamma, k, f, we) && ok;
+        o[i] = (_Float16)f;
+        if (Weff) Weff[(long)k * ldw + n] = we;   // (only this thread reads or writes element (k, n))
+    }
+    *reinterpret_cast<f16x8*>(Wt16 + idx * 8) = o;
+    if (!ok) *bad = 1;
+}
+void launch_pack_wt16_f16(const float* W, int ldw, const float* gamma, float* Weff, void* Wt16, int* bad, int K, int N, hipStream_t st) {
+    AUR_REQUIRE(N % 16 == 0 && K % 32 == 0 && ldw >= N && bad, "pack_wt16_f16: shape");
+    const long total = (long)(N >> 4) * (K >> 5) * 64;
+    trace_launch("pack_wt16_f16_kernel");
+    hipLaunchKernelGGL(pack_wt16_f16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, W, ldw, gamma, Weff,
+                       reinterpret_cast<_Float16*>(Wt16), bad, K, N);
+    HIP_CHECK(hipGetLastError());
+}
+// c1 / c2 of the fp16 fold (fold_ln_vectors_kernel's order: 16 k-slices per column, combined in a fixed order, in double)
+__global__ __launch_bounds__(256) void fold_ln_f16_vectors_kernel(const float* __restrict__ W, int ldw, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, const float* __restrict__ bias,
+                                                                  float* __restrict__ c1, float* __restrict__ c2, int K, int N) {
+    __shared__ double p1[16][16], p2[16][16];
+    const int col = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int n = blockIdx.x * 16 + col;
+    const int k0 = (int)((long)K * sl / 16), k1 = (int)((long)K * (sl + 1) / 16);
+    double s1 = 0.0, s2 = 0.0;
+    if (n < N)
+        for (int k = k0; k < k1; ++k) {
+            float f, we;
+            f16_rule(W[(long)k * ldw + n], gamma, k, f, we);
+            s1 += (double)f;
+            s2 += (double)beta[k] * (double)we;
+        }
+    p1[sl][col] = s1;
+    p2[sl][col] = s2;
+    __syncthreads();
+    if (sl == 0 && n < N) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int i = 0; i < 16; ++i) {
+            t1 += p1[i][col];
+            t2 += p2[i][col];
+        }
+        c1[n] = (float)t1;
+        c2[n] = (float)(t2 + (bias ? (double)bias[n] : 0.0));
+    }
+}
+void launch_fold_ln_f16(const float* W, int ldw, const float* gamma, const float* beta, const float* bias, float* Weff, void* Wt16,
+                        float* c1, float* c2, int* bad, int K, int N, hipStream_t st) {
+    AUR_REQUIRE(N % 16 == 0 && K % 32 == 0 && ldw >= N && gamma && beta, "fold_ln_f16: shape");
+    trace_launch("fold_ln_f16");
+    hipLaunchKernelGGL(fold_ln_f16_vectors_kernel, dim3((N + 15) / 16), dim3(256), 0, st, W, ldw, gamma, beta, bias, c1, c2, K, N);
+    HIP_CHECK(hipGetLastError());
+    launch_pack_wt16_f16(W, ldw, gamma, Weff, Wt16, bad, K, N, st);   // (same stream: runs after the sums have read W)
+}
+
 // PREC = 1: every fp32 operand is split exactly into three bf16 terms (x = h + m + l, round-to-nearest at each step) and a
 // product runs as six bf16 MFMAs with fp32 accumulation (h*h into `acc`; h*m, m*h, m*m, h*l, l*h into `lo`; the three dropped
 // terms are below 2^-25 of the product): 6 x 17 cycles per 16 x 16 x 32 block instead of 8 x 32 for v_mfma_f32_16x16x4_f32.
@@ -520,6 +610,21 @@ __device__ __forceinline__ void split3_bf16(const f32x4& x0, const f32x4& x1, bf
         h[i] = hh;
         m[i] = mm;
         l[i] = (__bf16)(r - (float)mm);
+    }
+}
+
+// PREC = 2: the 16 bytes a lane loads are 8 fp16 weights (pack_wt16_f16); each splits EXACTLY into two bf16 terms w = h + l (an
+// fp16 value has 11 significant bits: h keeps 8, the remainder at most 3, and bf16 has the fp32 exponent range).  With the three
+// terms of the fp32 activation that gives five MFMAs per product (h*h into `acc`; m*l, l*h, h*l, m*h into `lo`; the dropped l*l
+// term is below 2^-24 of the product).
+__device__ __forceinline__ void split2_f16(const f32x4& w, bf16x8& h, bf16x8& l) {
+    const f16x8 v = __builtin_bit_cast(f16x8, w);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float x = (float)v[i];
+        const __bf16 hh = (__bf16)x;
+        h[i] = hh;
+        l[i] = (__bf16)(x - (float)hh);
     }
 }
 

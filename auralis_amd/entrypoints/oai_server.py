@@ -275,8 +275,11 @@ def main():
     p.add_argument("--model", type=str, required=True, help="checkpoint directory in the reference's on-disk format")
     p.add_argument("--max_concurrency", type=int, default=8)
     p.add_argument("--vllm_logging_level", type=str, default="warn", help="accepted for CLI compatibility; unused")
+    p.add_argument("--gpt", choices=("fp32", "fp16"), default="fp32",
+                   help="fp16: per-layer GPT linears stored as fp16 for the decode GEMMs (aur_config.gpt_fp16); fp32: exact contract")
+    p.add_argument("--kv", choices=("fp32", "fp16"), default="fp32", help="fp16: K/V pool stored as fp16 (aur_config.kv_fp16)")
     a = p.parse_args()
-    tts = TTS(scheduler_max_concurrency=a.max_concurrency).from_pretrained(a.model)
+    tts = TTS(scheduler_max_concurrency=a.max_concurrency).from_pretrained(a.model, gpt=a.gpt, kv=a.kv)
     uvicorn.run(create_app(tts), host=a.host, port=a.port)
 
 

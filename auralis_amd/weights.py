@@ -140,6 +140,51 @@ def pack_gpt(gpt_sd: Dict[str, Tensor], xtts_sd: Dict[str, Tensor]) -> Dict[str,
     return {k: np.ascontiguousarray(v.float().numpy(), dtype=np.float32) for k, v in out.items()}
 
 
+# the four per-layer GPT linears and the LayerNorm whose gain the decode GEMM folds into each (None: no fold)
+GPT_FP16_LINEARS = (("attn.c_attn", "ln_1"), ("attn.c_proj", None), ("mlp.c_fc", "ln_2"), ("mlp.c_proj", None))
+
+
+def fp16_effective_matrix(w: np.ndarray, gamma=None):
+    """One matrix under aur_config.gpt_fp16 (see gpt_fp16_effective): (f, W'') -- the fp16 copy the decode GEMM streams and the
+    float32 effective weight; gamma = the LayerNorm gain folded into the rows (None: no fold)."""
+    w = np.asarray(w, dtype=np.float32)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        if gamma is None:
+            f = w.astype(np.float16)
+            weff = f.astype(np.float32)
+        else:
+            g = np.asarray(gamma, dtype=np.float32)[:, None]
+            f = (g * w).astype(np.float16)
+            weff = np.where(g != 0, f.astype(np.float32) / np.where(g != 0, g, np.float32(1)), w.astype(np.float16).astype(np.float32))
+    weff = weff.astype(np.float32)
+    if not (np.isfinite(w).all() and np.isfinite(f).all() and np.isfinite(weff).all()):
+        raise ValueError("gpt_fp16: a weight is not finite or leaves the fp16 range after LayerNorm folding")
+    return f, weff
+
+
+def gpt_fp16_effective(gpt_sd: Dict[str, Tensor]) -> Dict[str, Tensor]:
+    """Host mirror of aur_config.gpt_fp16 (include/auralis_amd.h): the GPT state dict (on-disk key names, as GPTOracle and pack_all
+    take it) with every per-layer linear weight replaced by the effective weight W'' the fp16 engine computes with.
+      c_proj pairs:                f = fp16_rne(W),                W'' = f
+      c_attn / ln_1, c_fc / ln_2:  f = fp16_rne(fp32(g[k] W[k][n])), W''[k][n] = fp32(f / g[k])  (fp16_rne(W[k][n]) where g[k] == 0)
+    float32 / float16 numpy arithmetic, round to nearest even.  Idempotent bit for bit.  Raises ValueError for a weight the engine
+    rejects (not finite, or beyond the fp16 range after folding).  Other tensors are passed through unchanged."""
+    out = dict(gpt_sd)
+    layers = sorted({int(k.split(".")[2]) for k in gpt_sd if k.startswith("gpt.h.")})
+
+    def arr(t):
+        return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t
+    for i in layers:
+        for lin, ln in GPT_FP16_LINEARS:
+            key = f"gpt.h.{i}.{lin}.weight"
+            try:
+                _, weff = fp16_effective_matrix(arr(gpt_sd[key]), None if ln is None else arr(gpt_sd[f"gpt.h.{i}.{ln}.weight"]))
+            except ValueError as e:
+                raise ValueError(f"{key}: {e}") from None
+            out[key] = torch.from_numpy(weff) if isinstance(gpt_sd[key], torch.Tensor) else weff
+    return out
+
+
 def pack_all(gpt_sd, xtts_sd) -> Dict[str, np.ndarray]:
     d = pack_vocoder(xtts_sd)
     d.update(pack_gpt(gpt_sd, xtts_sd))

@@ -73,6 +73,17 @@ typedef struct aur_config {
                                  free by then.  0 = default max_seqs / 8 (8 at 64 slots); 1 = never hold */
     int32_t urgent_rows;      /* running sequences the engine fills up to while a latency-critical sequence (aur_seq_desc.priority > 0)
                                  waits or runs.  0 = default max_seqs / 4; max_seqs = no cap */
+    int32_t gpt_fp16;         /* 1 = the four per-layer GPT linears (attn.c_attn, attn.c_proj, mlp.c_fc, mlp.c_proj) stay in HBM as
+                                 fp16 for the decode GEMMs (half their bytes); every product is still computed to fp32 accuracy, so
+                                 the mode is the exact model on the effective weights W'' defined here:
+                                   c_proj pairs:  f = fp16_rne(W), W'' = f;
+                                   c_attn with ln_1, c_fc with ln_2 (gain g, bias b): f[k][n] = fp16_rne(fp32(g[k] * W[k][n])),
+                                   W''[k][n] = fp32(f[k][n] / g[k]) (fp16_rne(W[k][n]) where g[k] == 0); the decode GEMM streams f.
+                                 The prompt-row GEMMs and second_pass run on W'' too (the engine keeps W'' in place of W).  The rule
+                                 is idempotent: an engine loaded with W'' computes bitwise what one loaded with W does.  A matrix
+                                 that is not finite or leaves the fp16 range after folding makes aur_load_weights fail with
+                                 AUR_E_INVALID; gpt_fp16 together with gemm_f32_exact makes aur_engine_create fail with
+                                 AUR_E_INVALID.  0 (default) = fp32 weights, bit-exact contract */
 } aur_config;
 
 /* One named fp32 tensor.  Names are the packed names produced by auralis_amd/weights.py from the
@@ -268,7 +279,9 @@ int aur_dbg_gemm(aur_engine* e, const float* X, const float* W, float* out, int3
 /* Decode-regime GEMM (gemm_rows_kernel: full-K workgroups, fused LayerNorm prologue and bias / gelu / residual epilogue;
  * replaces one GPT2Block linear of vLLM's GPT2Attention / GPT2MLP at M = live sequences, vllm_mm_gpt.py:757-761):
  * out[M][N] = epi(LN?(X[M][K]) @ W[K][N] + bias), epi 0 = bias, 1 = bias + gelu_new, 2 = out += (.. + bias).
- * ln != 0 applies LayerNorm(gamma, beta, eps 1e-5) to the rows of X first (K must be 1024).  K in {1024, 4096}. */
+ * ln != 0 applies LayerNorm(gamma, beta, eps 1e-5) to the rows of X first (K must be 1024).  K in {1024, 4096}.
+ * Follows the engine's mode: under aur_config.gpt_fp16 W is converted by that rule (fp16 copy, effective weights W'') and the
+ * kernel runs its fp16-weight arithmetic, as for the four per-layer GEMMs; aur_dbg_gemm_rows_ksplit_stress likewise. */
 int aur_dbg_gemm_rows(aur_engine* e, const float* X, const float* W, const float* bias, const float* gamma,
                       const float* beta, float* out, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t ln);
 /* Stress of the decode GEMM's K-split form (the K = 4096 -> 1024 projection at M <= 32 live sequences, same reference linear): `iters`

@@ -4,7 +4,8 @@
 //     stream really comes from HBM), next to the SAME launch with its tile loads and MFMAs compiled out (gemm_rows_kernel.inc,
 //     AUR_GR_NO_DATA = 1): the fixed cost of a launch -- boundary, argument fetch, epilogue inputs, LDS reduction, epilogue;
 //   * the decode attention launch alone by context length;
-//   * the decode layer chained over 30 layers of distinct weights and K/V pools, with and without attention.
+//   * the decode layer chained over 30 layers of distinct weights and K/V pools, with and without attention;
+// every GEMM in the three arithmetics: prec 0 (exact f32), 1 (bf16 x 3 split), 2 (fp16 weights, aur_config.gpt_fp16).
 // Build + run:  bash tools/gemm_bench.sh <tag> <M> [<M> ...]      (the A/B workgroup shapes of rounds 3-4 are in the git history)
 #include <algorithm>
 #include <cmath>
@@ -113,6 +114,8 @@ int main(int argc, char** argv) {
     HIP_CHECK(hipMalloc(&ksp_cnt, (size_t)kGemmKspTiles * 4));
     HIP_CHECK(hipMemset(ksp_cnt, 0, (size_t)kGemmKspTiles * 4));
     float* act = dalloc((size_t)256 * 4096, 0.5f, 22);
+    int* bad = nullptr;   // (launch_pack_wt16_f16's range flag: the seeded weights are far inside the fp16 range)
+    HIP_CHECK(hipMalloc(&bad, sizeof(int)));
     float* att = dalloc((size_t)256 * 1024, 0.5f, 23);
     float* qb = dalloc((size_t)256 * 1024, 0.f, 24);
 
@@ -156,25 +159,31 @@ int main(int argc, char** argv) {
     const int NREP = getenv("NREP") ? atoi(getenv("NREP")) : 24;   // distinct weight matrices per shape (NREP=1: the stream comes from L2)
     if (!quick)
         for (const Shape& s : shapes) {
-            std::vector<float*> wt(NREP);
+            std::vector<float*> wt(NREP), wt16(NREP);   // (wt16: the fp16 copies prec 2 streams, aur_config.gpt_fp16)
             float* wsrc = dalloc((size_t)s.K * s.N, 0.05f, 11);
             for (int r = 0; r < NREP; ++r) {
                 HIP_CHECK(hipMalloc(&wt[r], (size_t)s.K * s.N * 4));
+                HIP_CHECK(hipMalloc(&wt16[r], (size_t)s.K * s.N * 2));
                 launch_pack_wt16(wsrc, s.N, wt[r], s.K, s.N, st);
+                launch_pack_wt16_f16(wsrc, s.N, nullptr, nullptr, wt16[r], bad, s.K, s.N, st);
             }
             HIP_CHECK(hipStreamSynchronize(st));
-            for (int prec : {1, 0}) {
+            for (int prec : {1, 0, 2}) {
                 const GemmRowsShape g = gemm_rows_shape(M, s.N, s.K, s.ln);
+                const std::vector<float*>& w = prec == 2 ? wt16 : wt;
                 int it = 0;
-                const float us = time_us(st, 480, [&] { launch_gemm_rows(make_args(s, wt[it++ % NREP], prec), s.ln, s.epi, st); });
+                const float us = time_us(st, 480, [&] { launch_gemm_rows(make_args(s, w[it++ % NREP], prec), s.ln, s.epi, st); });
                 it = 0;
-                const float us0 = time_us(st, 480, [&] { launch_gemm_rows_nodata(make_args(s, wt[it++ % NREP], prec), s.ln, s.epi, st); });
-                const double mb = 4.0 * ((double)s.K * s.N + (double)M * s.K + (double)M * s.N * (s.epi == kEpiResidual ? 2 : 1)) / 1e6;
+                const float us0 = time_us(st, 480, [&] { launch_gemm_rows_nodata(make_args(s, w[it++ % NREP], prec), s.ln, s.epi, st); });
+                const double mb = ((prec == 2 ? 2.0 : 4.0) * s.K * s.N + 4.0 * ((double)M * s.K + (double)M * s.N * (s.epi == kEpiResidual ? 2 : 1))) / 1e6;
                 printf("%s M=%d rows/wg=%2d cols/wg=%2d waves=%2d ksp=%d nt=%d prec=%d : %6.2f us per launch (%.2f TB/s) | fixed (no tile loads, no MFMAs) %5.2f us\n",
                        s.name, M, 16 * g.mt, 16 * g.ntl, g.nw, g.ksp, (int)g.nt, prec, us, mb / us, us0);
                 fflush(stdout);
             }
-            for (int r = 0; r < NREP; ++r) HIP_CHECK(hipFree(wt[r]));
+            for (int r = 0; r < NREP; ++r) {
+                HIP_CHECK(hipFree(wt[r]));
+                HIP_CHECK(hipFree(wt16[r]));
+            }
             HIP_CHECK(hipFree(wsrc));
         }
     // ---- decode attention alone, by context length (all rows at the same position): intercept = the launch's fixed chain,
@@ -193,6 +202,7 @@ int main(int argc, char** argv) {
     // ---- the decode layer chained over 30 layers with distinct weights (1.5 GB) and K/V pools (127 MB read per attention launch)
     {
         std::vector<float*> wq(n_layers), wp(n_layers), wf(n_layers), w2(n_layers);
+        std::vector<float*> hq(n_layers), hp(n_layers), hf(n_layers), h2(n_layers);   // fp16 copies (prec 2)
         float* src = dalloc((size_t)4096 * 1024, 0.05f, 21);
         for (int l = 0; l < n_layers; ++l) {
             HIP_CHECK(hipMalloc(&wq[l], (size_t)3072 * 1024 * 4));
@@ -203,18 +213,27 @@ int main(int argc, char** argv) {
             launch_pack_wt16(src, 1024, wp[l], 1024, 1024, st);
             launch_pack_wt16(src, 4096, wf[l], 1024, 4096, st);
             launch_pack_wt16(src, 1024, w2[l], 4096, 1024, st);
+            HIP_CHECK(hipMalloc(&hq[l], (size_t)3072 * 1024 * 2));
+            HIP_CHECK(hipMalloc(&hp[l], (size_t)1024 * 1024 * 2));
+            HIP_CHECK(hipMalloc(&hf[l], (size_t)4096 * 1024 * 2));
+            HIP_CHECK(hipMalloc(&h2[l], (size_t)4096 * 1024 * 2));
+            launch_pack_wt16_f16(src, 3072, nullptr, nullptr, hq[l], bad, 1024, 3072, st);
+            launch_pack_wt16_f16(src, 1024, nullptr, nullptr, hp[l], bad, 1024, 1024, st);
+            launch_pack_wt16_f16(src, 4096, nullptr, nullptr, hf[l], bad, 1024, 4096, st);
+            launch_pack_wt16_f16(src, 1024, nullptr, nullptr, h2[l], bad, 4096, 1024, st);
         }
         HIP_CHECK(hipStreamSynchronize(st));
         auto chain = [&](bool attn, int prec) {
+            const bool h = prec == 2;
             for (int l = 0; l < n_layers; ++l) {
                 float* kvl = kv + (size_t)l * kv_blocks * kKvBlockElems;
-                GemmRowsArgs a = make_args(shapes[0], wq[l], prec);
+                GemmRowsArgs a = make_args(shapes[0], h ? hq[l] : wq[l], prec);
                 a.kv_layer = kvl;
                 launch_gemm_rows(a, true, kEpiQkv, st);
                 if (attn) launch_paged_attention(qb, kvl, drm, 66, att, M, st, MTT, false);
-                launch_gemm_rows(make_args(shapes[1], wp[l], prec), false, kEpiResidual, st);
-                launch_gemm_rows(make_args(shapes[2], wf[l], prec), true, kEpiBiasGelu, st);
-                launch_gemm_rows(make_args(shapes[3], w2[l], prec), false, kEpiResidual, st);
+                launch_gemm_rows(make_args(shapes[1], h ? hp[l] : wp[l], prec), false, kEpiResidual, st);
+                launch_gemm_rows(make_args(shapes[2], h ? hf[l] : wf[l], prec), true, kEpiBiasGelu, st);
+                launch_gemm_rows(make_args(shapes[3], h ? h2[l] : w2[l], prec), false, kEpiResidual, st);
             }
         };
         if (getenv("DUAL")) {
@@ -260,7 +279,7 @@ int main(int argc, char** argv) {
             }
         }
         for (int attn : {0, 1})
-            for (int prec : {0, 1}) {
+            for (int prec : {0, 1, 2}) {
                 const float us = time_us(st, 20, [&] { chain(attn != 0, prec); });
                 printf("chain of 30 x (qkv,%s proj, fc, proj2) M=%d prec=%d: %.1f us per layer (%.3f ms per step)\n", attn ? " attention," : "", M,
                        prec, us / n_layers, us / 1000);
