@@ -107,7 +107,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // LDS crossbar (~100 cycles, and a counted wait behind it).  J = 1, 2: DPP quad permutations; 4: two row shifts, each written to the
 // banks (groups of four lanes) it serves; 8: row rotation; 16, 32: gfx950's v_permlane16_swap / v_permlane32_swap of the register with
 // itself (results {R0,R0,R2,R2} / {R1,R1,R3,R3} by 16-lane rows, resp. {lower,lower} / {upper,upper} by halves) and a select on the
-// lane's own bit.  All 64 lanes active.  aur_dbg_lane_xor_selftest (engine.hip) checks every J against __shfl_xor on the GPU.
+// lane's own bit.  All 64 lanes active.  aur_dbg_lane_xor_selftest (dbg_harness.hip) checks every J against __shfl_xor on the GPU.
 template <int J>
 __device__ __forceinline__ int lane_xor(int x) {
     static_assert(J == 1 || J == 2 || J == 4 || J == 8 || J == 16 || J == 32, "lane_xor: a power of two below 64");

@@ -12,8 +12,8 @@
 #include <vector>
 
 #include "cond_kernels.h"
+#include "dev_buf.h"
 #include "gpt_kernels.h"
-// (included by engine.hip after its DevBuf definition)
 
 namespace aur {
 

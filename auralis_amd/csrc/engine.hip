@@ -20,67 +20,17 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/auralis_amd.h"
-#include "gpt_kernels.h"
+#include "abi_internal.h"
+#include "cond_net.h"
+#include "gpt_host.h"
 #include "vocoder_kernels.h"
 
 namespace aur {
 
-static thread_local std::string g_last_error;
+thread_local std::string g_last_error;
 
 constexpr int kProfileEvery = 64;   // profile mode default: every 64th decode step is followed by the per-kind replay batches (profile_replay)
 constexpr int kProj2Slabs = 4;   // split-K slabs of the prompt-row MLP projection (forward_rows)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    void ensure(size_t n) {
-        if (n <= bytes) return;
-        if (p) HIP_CHECK(hipFree(p));
-        p = nullptr;
-        bytes = 0;
-        HIP_CHECK(hipMalloc(&p, n));
-        bytes = n;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <class T>
-    T* as() const {
-        return reinterpret_cast<T*>(p);
-    }
-};
-
-struct PinBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~PinBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    void ensure(size_t n) {
-        if (n <= bytes) return;
-        if (p) HIP_CHECK(hipHostFree(p));
-        p = nullptr;
-        HIP_CHECK(hipHostMalloc(&p, n, hipHostMallocDefault));
-        bytes = n;
-    }
-    template <class T>
-    T* as() const {
-        return reinterpret_cast<T*>(p);
-    }
-};
-
-}  // namespace aur
-#include "cond_net.h"   // (uses DevBuf)
-namespace aur {
 
 // Pinned result block of one vocoder batch: the D2H copies land here and aur_result.wav / .latents point straight into
 // it (no second host copy); the block returns to the pool when the last sequence of the batch is released.
@@ -129,19 +79,6 @@ __global__ __launch_bounds__(256) void init_slots_kernel(const SlotInit* __restr
         ignore_stop[s.slot] = s.ignore_stop;
         seed[s.slot] = s.seed;
     }
-}
-
-// Test support (aur_dbg_gemm_rows_ksplit_stress): background HBM / L2 traffic on a second stream.  Every workgroup streams a
-// 64 KiB-aligned share of `src` (>= 32 KiB per CU per launch, the guide's "uneven load" rule for cross-workgroup hand-off tests)
-// and leaves one partial sum per workgroup so that the loads cannot be dropped.
-__global__ __launch_bounds__(256) void stress_load_kernel(const float4* __restrict__ src, float* __restrict__ sink, long n_vec) {
-    float acc = 0.f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_vec; i += (long)gridDim.x * 256) {
-        const float4 v = src[i];
-        acc += v.x + v.y + v.z + v.w;
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) atomicAdd(sink + blockIdx.x, acc);
 }
 
 // Row workspace of one GPT forward chain (prefill uses chain 0; decode can run two chains on two streams).
@@ -224,17 +161,14 @@ public:
         ints(temperature_, S); ints(top_p_, S); ints(top_k_, S); ints(rep_, S); ints(max_tokens_, S);
         ints(ignore_stop_, S); ints(seed_, S);
         ints(block_tables_, (size_t)(S + 1) * kMaxBlocks);   // row S: pseudo-slot used to prefill a speaker prefix
-        seen_.ensure((size_t)S * kSeenStride);
-        HIP_CHECK(hipMemsetAsync(seen_.p, 0, (size_t)S * kSeenStride, st_));
+        seen_.zeros((size_t)S * kSeenStride, st_);
         latents_.ensure((size_t)S * kMaxLatRows * kHidden * sizeof(float));
         spk_table_.ensure((size_t)cfg_.max_speakers * 32 * kHidden * sizeof(float));
         spk_emb_.ensure((size_t)cfg_.max_speakers * 512 * sizeof(float));
         voc_cond_.ensure((size_t)cfg_.max_speakers * kCondStride * sizeof(float));
-        zero_bias_.ensure(4096 * sizeof(float));
-        HIP_CHECK(hipMemsetAsync(zero_bias_.p, 0, 4096 * sizeof(float), st_));
+        zero_bias_.zeros(4096 * sizeof(float), st_);
         ksp_buf_.ensure((size_t)kGemmKspTiles * 16 * 256 * sizeof(float));   // K-split partial tiles of the small-M mlp projection
-        ksp_cnt_.ensure((size_t)kGemmKspTiles * sizeof(unsigned));
-        HIP_CHECK(hipMemsetAsync(ksp_cnt_.p, 0, (size_t)kGemmKspTiles * sizeof(unsigned), st_));
+        ksp_cnt_.zeros((size_t)kGemmKspTiles * sizeof(unsigned), st_);
         h_block_tables_.assign((size_t)(S + 1) * kMaxBlocks, 0);
         spk_info_.assign(cfg_.max_speakers, SpeakerInfo{});
         slot_owner_.assign(S, nullptr);
@@ -291,6 +225,7 @@ public:
     }
 
     void use() { HIP_CHECK(hipSetDevice(device_)); }
+    DbgCtx dbg_ctx() const { return {device_, st_, st_voc_, gemm_prec_, gpt_f16_, gemm_presplit_, ksp_buf_.as<float>(), ksp_cnt_.as<unsigned>()}; }
 
     // ------------------------------------------------------------------ weights
     void load(const aur_tensor_desc* t, size_t n) {
@@ -301,39 +236,37 @@ public:
             AUR_REQUIRE(t[i].name && t[i].data && t[i].numel > 0, "bad tensor desc");
             Tensor& dst = w_[t[i].name];
             if (!dst.buf) dst.buf.reset(new DevBuf());
-            dst.buf->ensure((size_t)t[i].numel * sizeof(float));
+            dst.buf->upload(t[i].data, (size_t)t[i].numel * sizeof(float));
             dst.numel = t[i].numel;
             dst.f16_eff = false;
-            HIP_CHECK(hipMemcpy(dst.buf->p, t[i].data, (size_t)t[i].numel * sizeof(float), hipMemcpyHostToDevice));
         }
         voc_ready_ = false;
         gpt_ready_ = false;
         if (gpt_f16_) check_gpt_f16();
     }
-    // aur_config.gpt_fp16: once every per-layer matrix and its LayerNorm gain are loaded, a matrix the rule rejects (not finite, or
-    // beyond the fp16 range after folding) fails the load that completed the set, before anything is converted
-    // the four per-layer matrices of layer prefix p, with the LayerNorm gain folded into each (empty: none)
-    struct F16Mat {
-        std::string w, gamma;
+    // The four linears of a GPT layer, in the order the decode chain runs them: tensor name (.w / .b) under the layer's prefix, the
+    // LayerNorm in front of it (folded into its decode operand) or none, and its shape.
+    struct LinearSpec {
+        const char *name, *ln;
         int K, N;
     };
-    static std::vector<F16Mat> gpt_f16_mats(const std::string& p) {
-        return {{p + "attn.c_attn.w", p + "ln_1.w", kHidden, 3 * kHidden}, {p + "attn.c_proj.w", "", kHidden, kHidden},
-                {p + "mlp.c_fc.w", p + "ln_2.w", kHidden, 4 * kHidden}, {p + "mlp.c_proj.w", "", 4 * kHidden, kHidden}};
-    }
+    static constexpr LinearSpec kLinears[4] = {{"attn.c_attn", "ln_1", kHidden, 3 * kHidden}, {"attn.c_proj", nullptr, kHidden, kHidden},
+                                               {"mlp.c_fc", "ln_2", kHidden, 4 * kHidden}, {"mlp.c_proj", nullptr, 4 * kHidden, kHidden}};
+    static std::string layer_prefix(int i) { return "gpt.h." + std::to_string(i) + "."; }
+    // aur_config.gpt_fp16: once every per-layer matrix and its LayerNorm gain are loaded, a matrix the rule rejects (not finite, or
+    // beyond the fp16 range after folding) fails the load that completed the set, before anything is converted
     void check_gpt_f16() {
         auto has = [&](const std::string& n, int64_t numel) { auto it = w_.find(n); return it != w_.end() && it->second.numel == numel; };
-        std::vector<F16Mat> mats;
         for (int i = 0; i < cfg_.n_layer; ++i)
-            for (auto& m : gpt_f16_mats("gpt.h." + std::to_string(i) + "."))
-                if (!has(m.w, (int64_t)m.K * m.N) || (!m.gamma.empty() && !has(m.gamma, m.K))) return;   // not complete yet (or misshapen:
-                else mats.push_back(m);                                                                   // ensure_gpt reports that)
+            for (const LinearSpec& m : kLinears)   // not complete yet (or misshapen: ensure_gpt reports that)
+                if (!has(layer_prefix(i) + m.name + ".w", (int64_t)m.K * m.N) || (m.ln && !has(layer_prefix(i) + m.ln + ".w", m.K))) return;
         DevBuf dbad, scratch;
-        dbad.ensure(sizeof(int));
+        dbad.zeros(sizeof(int), st_);
         scratch.ensure((size_t)4 * kHidden * kHidden * 2);
-        HIP_CHECK(hipMemsetAsync(dbad.p, 0, sizeof(int), st_));
-        for (auto& m : mats)
-            launch_pack_wt16_f16(W(m.w), m.N, m.gamma.empty() ? nullptr : W(m.gamma), nullptr, scratch.p, dbad.as<int>(), m.K, m.N, st_);
+        for (int i = 0; i < cfg_.n_layer; ++i)
+            for (const LinearSpec& m : kLinears)
+                launch_pack_wt16_f16(W(layer_prefix(i) + m.name + ".w"), m.N, m.ln ? W(layer_prefix(i) + m.ln + ".w") : nullptr, nullptr, scratch.p,
+                                     dbad.as<int>(), m.K, m.N, st_);
         int bad = 0;
         HIP_CHECK(hipMemcpyAsync(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost, st_));
         HIP_CHECK(hipStreamSynchronize(st_));
@@ -772,7 +705,6 @@ public:
         use();
         ensure_gpt();
         if (fail_at_step_ > 0 && --fail_at_step_ == 0) {   // AUR_TEST_FAIL_STEP=n: fault injection for the recovery test
-            std::vector<Seq*> dummy;
             throw HipError("injected failure (AUR_TEST_FAIL_STEP)");
         }
         bool worked = false;
@@ -871,7 +803,7 @@ public:
             if (slot_owner_[i] && slot_owner_[i]->state == SeqState::RUNNING) active.push_back(i);
         if (!active.empty()) {
             HIP_CHECK(hipEventRecord(ev_a_, st_));
-            decode(active);
+            decode_pipelined(active);
             worked = true;
         }
         {
@@ -987,370 +919,6 @@ public:
     }
 
     // ------------------------------------------------------------------ debug entry points
-    // prefill-regime GEMM (gemm_tile_kernel / gemm_tile_split_kernel, the arithmetic the engine was configured with) on host data: out = X @ W
-    void dbg_gemm(const float* X, const float* Wm, float* out, int M, int N, int K) {
-        use();
-        DevBuf dx, dw, dp;
-        dx.ensure((size_t)M * K * 4);
-        dw.ensure((size_t)K * N * 4);
-        dp.ensure((size_t)M * N * 4);
-        HIP_CHECK(hipMemcpy(dx.p, X, (size_t)M * K * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dw.p, Wm, (size_t)K * N * 4, hipMemcpyHostToDevice));
-        DevBuf ds;   // the pre-split weight operand, as ensure_gpt() prepares it for the prompt-row GEMMs
-        if (gemm_prec_ == 1 && gemm_presplit_ && N % 128 == 0) {
-            ds.ensure((size_t)3 * K * N * 2);
-            launch_pack_wsplit(dw.as<float>(), N, ds.p, K, N, st_);
-        }
-        launch_gemm_tile(dx.as<float>(), K, dw.as<float>(), dp.as<float>(), M, N, K, st_, nullptr, gemm_prec_, 1, ds.p);
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipMemcpy(out, dp.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    }
-    // decode-regime GEMM on host data: out = epi(LN?(X) @ W + bias); W is the plain [K][N] matrix, packed on the device by
-    // the same pack_wt16 the engine uses at load time.  epi: 0 bias, 1 bias + gelu_new, 2 out += (X @ W + bias).
-    void dbg_gemm_rows(const float* X, const float* Wm, const float* bias, const float* gamma, const float* beta, float* out,
-                       int M, int N, int K, int epi, bool ln) {
-        use();
-        AUR_REQUIRE(epi >= 0 && epi <= 2, "dbg_gemm_rows: epi in {0,1,2}");
-        AUR_REQUIRE(!ln || (gamma && beta), "dbg_gemm_rows: LN needs gamma and beta");
-        DevBuf dx, dw, dwt, db, dg, dbe, dout;
-        const int mtt = (M + 63) / 64 * 4;                      // 16-row tiles of the packed activation buffers
-        const bool out_packed = (epi == kEpiBiasGelu || epi == kEpiResidual);
-        std::vector<float> hx((size_t)mtt * 16 * K, 0.f), ho((size_t)mtt * 16 * N, 0.f);
-        for (int m = 0; m < M; ++m)
-            for (int k = 0; k < K; ++k) hx[pk_off(m, k, mtt)] = X[(size_t)m * K + k];
-        for (int m = 0; m < M; ++m)
-            for (int n = 0; n < N; ++n) ho[out_packed ? pk_off(m, n, mtt) : (size_t)m * N + n] = out[(size_t)m * N + n];
-        dx.ensure(hx.size() * 4);
-        dw.ensure((size_t)K * N * 4);
-        dwt.ensure((size_t)K * N * 4);
-        dout.ensure(ho.size() * 4);
-        HIP_CHECK(hipMemcpy(dx.p, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dw.p, Wm, (size_t)K * N * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dout.p, ho.data(), ho.size() * 4, hipMemcpyHostToDevice));
-        if (bias) {
-            db.ensure((size_t)N * 4);
-            HIP_CHECK(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
-        }
-        DevBuf dst;
-        if (ln) {
-            // LayerNorm partials per 16-column tile, as the residual-stream producers emit them (GemmRowsArgs)
-            std::vector<float2> hs((size_t)mtt * 16 * 64, make_float2(0.f, 0.f));
-            for (int m = 0; m < M; ++m)
-                for (int t = 0; t < 64; ++t) {
-                    float sm = 0.f, m2 = 0.f;
-                    for (int c = 0; c < 16; ++c) sm += X[(size_t)m * K + 16 * t + c];
-                    const float mu = sm * (1.0f / 16.0f);
-                    for (int c = 0; c < 16; ++c) {
-                        const float d = X[(size_t)m * K + 16 * t + c] - mu;
-                        m2 += d * d;
-                    }
-                    hs[(size_t)m * 64 + t] = make_float2(mu, m2);
-                }
-            dst.ensure(hs.size() * sizeof(float2));
-            HIP_CHECK(hipMemcpy(dst.p, hs.data(), hs.size() * sizeof(float2), hipMemcpyHostToDevice));
-            dg.ensure((size_t)K * 4);
-            dbe.ensure((size_t)K * 4);
-            HIP_CHECK(hipMemcpy(dg.p, gamma, (size_t)K * 4, hipMemcpyHostToDevice));
-            HIP_CHECK(hipMemcpy(dbe.p, beta, (size_t)K * 4, hipMemcpyHostToDevice));
-        }
-        GemmRowsArgs a{};
-        DevBuf dsc, dvec, dbad;
-        if (gpt_f16_) {   // aur_config.gpt_fp16: the fp16 decode copy, as ensure_gpt() makes it for the four per-layer GEMMs
-            dbad.ensure(sizeof(int));
-            HIP_CHECK(hipMemsetAsync(dbad.p, 0, sizeof(int), st_));
-            if (ln) {
-                dvec.ensure((size_t)2 * N * 4);
-                launch_fold_ln_f16(dw.as<float>(), N, dg.as<float>(), dbe.as<float>(), bias ? db.as<float>() : nullptr, nullptr, dwt.p,
-                                   dvec.as<float>(), dvec.as<float>() + N, dbad.as<int>(), K, N, st_);
-                a.ln_c1 = dvec.as<float>();
-                a.bias = dvec.as<float>() + N;
-            } else {
-                launch_pack_wt16_f16(dw.as<float>(), N, nullptr, nullptr, dwt.p, dbad.as<int>(), K, N, st_);
-                if (!bias) {   // the kernel loads its bias unconditionally
-                    db.ensure((size_t)N * 4);
-                    HIP_CHECK(hipMemsetAsync(db.p, 0, (size_t)N * 4, st_));
-                }
-                a.bias = db.as<float>();
-            }
-            int bad = 0;
-            HIP_CHECK(hipMemcpyAsync(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost, st_));
-            HIP_CHECK(hipStreamSynchronize(st_));
-            AUR_REQUIRE(!bad, "dbg_gemm_rows: gpt_fp16 rejects these weights (not finite, or beyond the fp16 range after folding)");
-        } else if (ln) {   // LayerNorm folded into the weights, as ensure_gpt() does at load time
-            dsc.ensure((size_t)K * N * 4);
-            dvec.ensure((size_t)2 * N * 4);
-            launch_fold_ln(dw.as<float>(), N, dg.as<float>(), dbe.as<float>(), bias ? db.as<float>() : nullptr, dsc.as<float>(),
-                           dwt.as<float>(), dvec.as<float>(), dvec.as<float>() + N, K, N, st_);
-            a.ln_c1 = dvec.as<float>();
-            a.bias = dvec.as<float>() + N;
-        } else {
-            launch_pack_wt16(dw.as<float>(), N, dwt.as<float>(), K, N, st_);
-            if (!bias) {   // the kernel loads its bias unconditionally
-                db.ensure((size_t)N * 4);
-                HIP_CHECK(hipMemsetAsync(db.p, 0, (size_t)N * 4, st_));
-            }
-            a.bias = db.as<float>();
-        }
-        a.X = dx.as<float>(); a.xmt = mtt; a.Wt = dwt.as<float>(); a.M = M; a.N = N; a.K = K;
-        a.eps = 1e-5f; a.prec = gpt_f16_ ? 2 : gemm_prec_;
-        if ((long)((M + 15) / 16) * (N / 16) <= kGemmKspTiles) { a.ksp_buf = ksp_buf_.as<float>(); a.ksp_cnt = ksp_cnt_.as<unsigned>(); }
-        a.stats_in = ln ? dst.as<float2>() : nullptr;
-        a.out = dout.as<float>(); a.ldo = N; a.omt = mtt;
-        launch_gemm_rows(a, ln, (GemmRowsEpi)epi, st_);
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipMemcpy(ho.data(), dout.p, ho.size() * 4, hipMemcpyDeviceToHost));
-        for (int m = 0; m < M; ++m)
-            for (int n = 0; n < N; ++n) out[(size_t)m * N + n] = ho[out_packed ? pk_off(m, n, mtt) : (size_t)m * N + n];
-    }
-    // Stress of the K-split projection's cross-workgroup protocol (gemm_rows_kernel.inc, KSP: write-through partial tiles, drained
-    // vmcnt, device-scope ticket, sc0 sc1 read-back by the last arriver, counter reset for the next launch): `iters` back-to-back
-    // launches of the K = 4096 -> 1024 residual GEMM at M rows, no host synchronisation in between, on two alternating operand
-    // sets and beside a second stream that streams 256 MiB per launch, each compared word for word on the device with the UNSPLIT
-    // kernel's result on the matching operands.  A visibility bug shows up as a non-zero count (dbg_gemm_rows_ksplit_stress).
-    long long dbg_lane_xor_selftest(int blocks) {
-        use();
-        AUR_REQUIRE(blocks >= 1 && blocks <= 4096, "lane_xor selftest: 1..4096 workgroups");
-        DevBuf dcnt;
-        dcnt.ensure(8);
-        HIP_CHECK(hipMemsetAsync(dcnt.p, 0, 8, st_));
-        launch_lane_xor_selftest(0x9E3779B9u, blocks, dcnt.as<unsigned long long>(), st_);
-        unsigned long long bad = 0;
-        HIP_CHECK(hipMemcpyAsync(&bad, dcnt.p, 8, hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        return (long long)bad;
-    }
-    long long dbg_gemm_rows_ksplit_stress(int M, int iters) {
-        use();
-        const int K = 4 * kHidden, N = kHidden;
-        AUR_REQUIRE(M >= 1 && M <= 32 && iters >= 1, "ksplit stress: the split is used for M <= 32 rows");
-        AUR_REQUIRE(gemm_rows_shape(M, N, K, false).ksp > 1, "ksplit stress: the policy does not split at this M");
-        // TWO operand sets, alternated launch by launch: consecutive launches publish DIFFERENT partial tiles into ksp_buf, so a
-        // last arriver that read a stale partial (the previous launch's, left in a cache the sc0 sc1 read-back failed to bypass, or
-        // a ticket that ran ahead of its data) produces the wrong words -- on identical operands it would have produced the right ones.
-        const int mtt = 4;
-        const size_t nx = (size_t)mtt * 16 * K, nh = (size_t)mtt * 16 * N;
-        std::vector<float> hx(2 * nx), hw((size_t)K * N), hb(N), hh(2 * nh);
-        unsigned sd = 12345u + (unsigned)M;
-        auto rnd = [&] { sd = sd * 1664525u + 1013904223u; return (float)(sd >> 8) * (1.0f / 8388608.0f) - 1.0f; };
-        for (auto& v : hx) v = rnd();
-        for (auto& v : hw) v = 0.05f * rnd();
-        for (auto& v : hb) v = 0.1f * rnd();
-        for (auto& v : hh) v = rnd();
-        DevBuf dx, dw, dwt, db, dh0, dh, dref, dcnt, dload, dsink;
-        dx.ensure(hx.size() * 4); dw.ensure(hw.size() * 4); dwt.ensure(hw.size() * 4); db.ensure(hb.size() * 4);
-        dh0.ensure(hh.size() * 4); dh.ensure(nh * 4); dref.ensure(hh.size() * 4); dcnt.ensure(8);
-        HIP_CHECK(hipMemcpy(dx.p, hx.data(), hx.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dw.p, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(db.p, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dh0.p, hh.data(), hh.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemsetAsync(dcnt.p, 0, 8, st_));
-        if (gpt_f16_) {   // aur_config.gpt_fp16: the fp16 decode copy and arithmetic of the per-layer GEMMs
-            DevBuf dbad;
-            dbad.ensure(sizeof(int));
-            launch_pack_wt16_f16(dw.as<float>(), N, nullptr, nullptr, dwt.p, dbad.as<int>(), K, N, st_);
-            HIP_CHECK(hipStreamSynchronize(st_));
-        } else {
-            launch_pack_wt16(dw.as<float>(), N, dwt.as<float>(), K, N, st_);
-        }
-        GemmRowsArgs a{};
-        a.xmt = mtt; a.omt = mtt; a.Wt = dwt.as<float>(); a.M = M; a.N = N; a.K = K; a.bias = db.as<float>(); a.prec = gpt_f16_ ? 2 : gemm_prec_;
-        // references: no scratch -> the UNSPLIT kernel, one per operand set
-        HIP_CHECK(hipMemcpyAsync(dref.p, dh0.p, hh.size() * 4, hipMemcpyDeviceToDevice, st_));
-        for (int s = 0; s < 2; ++s) {
-            a.X = dx.as<float>() + s * nx; a.out = dref.as<float>() + s * nh;
-            launch_gemm_rows(a, false, kEpiResidual, st_);
-        }
-        // background load on the low-priority stream for the whole test: 256 MiB streamed per launch by 1024 workgroups (256 KiB
-        // each), a launch enqueued for every second split launch (~50 us of traffic against ~25 us per iteration), so that the
-        // split kernel's workgroups start unevenly and its partials, tickets and read-backs share L2 and the fabric with other traffic
-        const size_t load_bytes = (size_t)256 << 20;
-        dload.ensure(load_bytes);
-        dsink.ensure(1024 * 4);
-        HIP_CHECK(hipMemsetAsync(dload.p, 0, load_bytes, st_voc_));
-        HIP_CHECK(hipMemsetAsync(dsink.p, 0, 1024 * 4, st_voc_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        a.ksp_buf = ksp_buf_.as<float>(); a.ksp_cnt = ksp_cnt_.as<unsigned>();
-        auto split_launch = [&](int s) {
-            HIP_CHECK(hipMemcpyAsync(dh.p, dh0.as<float>() + s * nh, nh * 4, hipMemcpyDeviceToDevice, st_));
-            a.X = dx.as<float>() + s * nx; a.out = dh.as<float>();
-            launch_gemm_rows(a, false, kEpiResidual, st_);
-        };
-        for (int i = 0; i < iters; ++i) {
-            const int s = i & 1;
-            if ((i & 1) == 0)
-                hipLaunchKernelGGL(stress_load_kernel, dim3(1024), dim3(256), 0, st_voc_, dload.as<float4>(), dsink.as<float>(), (long)(load_bytes / 16));
-            if (i % 3 == 2) {   // two split launches on DIFFERENT data with nothing between them but the residual copy: the counter reset
-                split_launch(s ^ 1);   // and the scratch reuse are on the path; only the second one is checked
-            }
-            split_launch(s);
-            launch_count_mismatch(dh.p, dref.as<float>() + s * nh, (long)nh, dcnt.as<unsigned long long>(), st_);
-        }
-        HIP_CHECK(hipGetLastError());
-        unsigned long long bad = 0;
-        HIP_CHECK(hipMemcpyAsync(&bad, dcnt.p, 8, hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipStreamSynchronize(st_voc_));
-        return (long long)bad;
-    }
-    void dbg_paged_attention(const float* q, const float* k, const float* v, const int* ctx, int M, int ctx_max, int shared, bool half,
-                             float* out) {
-        use();
-        AUR_REQUIRE(M >= 1 && M <= 256 && ctx_max >= 1 && ctx_max <= kMaxBlocks * kKvBlockTokens, "dbg_paged_attention: 1..256 rows, context 1..1056");
-        AUR_REQUIRE(shared == 0 || shared == 16 || shared == 32, "dbg_paged_attention: shared prefix of 0, 16 or 32 tokens");
-        const int n_shared = shared / kKvBlockTokens, per_row = (ctx_max + kKvBlockTokens - 1) / kKvBlockTokens;
-        const long n_blocks = 1 + n_shared + (long)M * per_row;   // (block 0 stays empty: what a table entry past a row's blocks names)
-        std::vector<int> rm((size_t)M * kRowMetaStride, 0);
-        std::vector<float> pool((size_t)n_blocks * kKvBlockElems, 0.f);
-        for (int m = 0; m < M; ++m) {
-            AUR_REQUIRE(ctx[m] >= 1 && ctx[m] <= ctx_max && ctx[m] >= shared, "dbg_paged_attention: ctx[m] in [max(1, shared), ctx_max]");
-            int* r = &rm[(size_t)m * kRowMetaStride];
-            for (int b = 0; b < per_row; ++b) r[kRowMetaBt + b] = b < n_shared ? 1 + b : 1 + n_shared + m * per_row + b;
-            r[0] = ctx[m] - 1;
-            r[1] = m;
-            r[kRowMetaWblk] = r[kRowMetaBt + (ctx[m] - 1) / kKvBlockTokens];
-            for (int t = 0; t < ctx[m]; ++t) {
-                const int src = t < shared ? 0 : m;   // the shared tokens are row 0's
-                const int blk = r[kRowMetaBt + t / kKvBlockTokens];
-                for (int kvi = 0; kvi < 2; ++kvi) {
-                    const float* row = (kvi ? v : k) + ((size_t)src * ctx_max + t) * kHidden;
-                    for (int h = 0; h < kHeads; ++h)
-                        // ([block][K|V][head][token in block][64], gpt_kernels.hip: kv_offset)
-                        std::memcpy(&pool[((((size_t)blk * 2 + kvi) * kHeads + h) * kKvBlockTokens + t % kKvBlockTokens) * kHeadDim],
-                                    row + h * kHeadDim, kHeadDim * sizeof(float));
-                }
-            }
-        }
-        DevBuf dq, dpool, drm, dout;
-        dq.ensure((size_t)M * kHidden * 4);
-        drm.ensure(rm.size() * 4);
-        dout.ensure((size_t)M * kHidden * 4);
-        HIP_CHECK(hipMemcpy(dq.p, q, (size_t)M * kHidden * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(drm.p, rm.data(), rm.size() * 4, hipMemcpyHostToDevice));
-        if (half) {
-            std::vector<_Float16> ph(pool.size());
-            for (size_t i = 0; i < pool.size(); ++i) ph[i] = (_Float16)pool[i];
-            dpool.ensure(ph.size() * 2);
-            HIP_CHECK(hipMemcpy(dpool.p, ph.data(), ph.size() * 2, hipMemcpyHostToDevice));
-        } else {
-            dpool.ensure(pool.size() * 4);
-            HIP_CHECK(hipMemcpy(dpool.p, pool.data(), pool.size() * 4, hipMemcpyHostToDevice));
-        }
-        launch_paged_attention(dq.as<float>(), dpool.p, drm.as<int>(), kMaxBlocks, dout.as<float>(), M, st_, 0, half);
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)M * kHidden * 4, hipMemcpyDeviceToHost));
-    }
-    void dbg_prompt_attention(const float* q, const float* k, const float* v, const int* row_seq, const int* row_pos, int M, int n_seq,
-                              int ctx_max, int shared, bool half, float* out) {
-        use();
-        AUR_REQUIRE(M >= 1 && M <= 8192 && n_seq >= 1 && n_seq <= 64 && ctx_max >= 1 && ctx_max <= kMaxBlocks * kKvBlockTokens,
-                    "dbg_prompt_attention: 1..8192 rows, 1..64 sequences, context 1..1056");
-        AUR_REQUIRE(shared == 0 || shared == 16 || shared == 32, "dbg_prompt_attention: shared prefix of 0, 16 or 32 tokens");
-        const int n_shared = shared / kKvBlockTokens, per_seq = (ctx_max + kKvBlockTokens - 1) / kKvBlockTokens;
-        const long n_blocks = 1 + n_shared + (long)n_seq * per_seq;
-        std::vector<int> bt((size_t)n_seq * kMaxBlocks, 0);
-        std::vector<float> pool((size_t)n_blocks * kKvBlockElems, 0.f);
-        for (int sq = 0; sq < n_seq; ++sq) {
-            for (int b = 0; b < per_seq; ++b) bt[(size_t)sq * kMaxBlocks + b] = b < n_shared ? 1 + b : 1 + n_shared + sq * per_seq + b;
-            for (int t = 0; t < ctx_max; ++t) {
-                const int src = t < shared ? 0 : sq;
-                const int blk = bt[(size_t)sq * kMaxBlocks + t / kKvBlockTokens];
-                for (int kvi = 0; kvi < 2; ++kvi) {
-                    const float* row = (kvi ? v : k) + ((size_t)src * ctx_max + t) * kHidden;
-                    for (int h = 0; h < kHeads; ++h)
-                        std::memcpy(&pool[((((size_t)blk * 2 + kvi) * kHeads + h) * kKvBlockTokens + t % kKvBlockTokens) * kHeadDim],
-                                    row + h * kHeadDim, kHeadDim * sizeof(float));
-                }
-            }
-        }
-        std::vector<int> rs(row_seq, row_seq + M), rp(row_pos, row_pos + M);
-        for (int m = 0; m < M; ++m)
-            AUR_REQUIRE(rs[m] >= 0 && rs[m] < n_seq && rp[m] >= 0 && rp[m] < ctx_max, "dbg_prompt_attention: row_seq / row_pos out of range");
-        RowWs w;
-        w.st = st_;
-        const int n_qblk = upload_qblocks(w, rs, rp);
-        DevBuf dq, dpool, dbt, drs, drp, dout;
-        dq.ensure((size_t)M * kHidden * 4);
-        dout.ensure((size_t)M * kHidden * 4);
-        dbt.ensure(bt.size() * 4);
-        drs.ensure((size_t)M * 4);
-        drp.ensure((size_t)M * 4);
-        HIP_CHECK(hipMemcpy(dq.p, q, (size_t)M * kHidden * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dbt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(drs.p, rs.data(), (size_t)M * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(drp.p, rp.data(), (size_t)M * 4, hipMemcpyHostToDevice));
-        if (half) {
-            std::vector<_Float16> ph(pool.size());
-            for (size_t i = 0; i < pool.size(); ++i) ph[i] = (_Float16)pool[i];
-            dpool.ensure(ph.size() * 2);
-            HIP_CHECK(hipMemcpy(dpool.p, ph.data(), ph.size() * 2, hipMemcpyHostToDevice));
-        } else {
-            dpool.ensure(pool.size() * 4);
-            HIP_CHECK(hipMemcpy(dpool.p, pool.data(), pool.size() * 4, hipMemcpyHostToDevice));
-        }
-        launch_prompt_attention(dq.as<float>(), dpool.p, w.i_qblk.as<int2>(), n_qblk, drs.as<int>(), drp.as<int>(), dbt.as<int>(), kMaxBlocks,
-                                dout.as<float>(), st_, half);
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)M * kHidden * 4, hipMemcpyDeviceToHost));
-    }
-    void dbg_layernorm(const float* h, const float* gamma, const float* beta, float* out, int M) {
-        use();
-        DevBuf dh, dg, db, dout;
-        dh.ensure((size_t)M * kHidden * 4);
-        dg.ensure(kHidden * 4);
-        db.ensure(kHidden * 4);
-        dout.ensure((size_t)M * kHidden * 4);
-        HIP_CHECK(hipMemcpy(dh.p, h, (size_t)M * kHidden * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dg.p, gamma, kHidden * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(db.p, beta, kHidden * 4, hipMemcpyHostToDevice));
-        launch_rows_ln(nullptr, 0, nullptr, dh.as<float>(), dg.as<float>(), db.as<float>(), dout.as<float>(), M, 1e-5f, st_);
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)M * kHidden * 4, hipMemcpyDeviceToHost));
-    }
-    void dbg_conv1d(const float* x, const void* wp, const float* bias, const float* res, float* out,
-                    const int* lens, int B, int Cin, int Mtot, int Cout, int L, int KS, int DIL, int padl,
-                    float slope, int ups_s, int ups_p, bool f16) {
-        use();
-        const int Lout = L * std::max(1, ups_s);
-        DevBuf dx, dw, db, dr, dout, dl;
-        dx.ensure((size_t)B * Cin * L * 4);
-        const size_t wbytes = (size_t)Mtot * Cin * KS * (f16 ? 2 : 4);
-        dw.ensure(wbytes);
-        dout.ensure((size_t)B * Cout * Lout * 4);
-        dl.ensure((size_t)B * 4);
-        HIP_CHECK(hipMemcpy(dx.p, x, (size_t)B * Cin * L * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dw.p, wp, wbytes, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(dl.p, lens, (size_t)B * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemsetAsync(dout.p, 0, (size_t)B * Cout * Lout * 4, st_));
-        if (bias) {
-            db.ensure((size_t)Cout * 4);
-            HIP_CHECK(hipMemcpy(db.p, bias, (size_t)Cout * 4, hipMemcpyHostToDevice));
-        }
-        if (res) {
-            dr.ensure((size_t)B * Cout * Lout * 4);
-            HIP_CHECK(hipMemcpy(dr.p, res, (size_t)B * Cout * Lout * 4, hipMemcpyHostToDevice));
-        }
-        ConvArgs a{};
-        a.x = dx.as<float>();
-        a.wp = dw.as<float>();
-        a.wp16 = dw.p;
-        a.bias = bias ? db.as<float>() : nullptr;
-        a.res = res ? dr.as<float>() : nullptr;
-        a.out = dout.as<float>();
-        a.base_len = dl.as<int>();
-        a.len_mul = 1;
-        a.Cin = Cin; a.Mtot = Mtot; a.Cout = Cout;
-        a.x_stride = L; a.o_stride = Lout;
-        a.x_bstride = (long)Cin * L; a.o_bstride = (long)Cout * Lout;
-        a.padl = padl; a.slope = slope; a.ups_s = ups_s; a.ups_p = ups_p;
-        a.max_len = *std::max_element(lens, lens + B);
-        a.B = B;
-        if (f16)
-            launch_conv1d_f16(a, KS, DIL, st_);
-        else
-            launch_conv1d(a, KS, DIL, st_);
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)B * Cout * Lout * 4, hipMemcpyDeviceToHost));
-    }
     void dbg_prefill(const int* text_ids, int n_text, uint64_t key, float rep_penalty, float* lnf_rows_out,
                      float* logits_out) {
         use();
@@ -1361,11 +929,15 @@ public:
         d.repetition_penalty = rep_penalty; d.max_tokens = 1; d.seed = 0; d.ignore_stop = 1;
         const uint64_t id = submit(d);
         dbg_logits_.ensure((size_t)kMelVocab * 4);
-        dbg_capture_ = true;
-        share_prefix_now_ = false;
-        step(nullptr, nullptr);
-        share_prefix_now_ = true;
-        dbg_capture_ = false;
+        {
+            struct Restore {   // also when the step throws
+                Engine& e;
+                ~Restore() { e.share_prefix_now_ = true, e.dbg_capture_ = false; }
+            } restore{*this};
+            dbg_capture_ = true;
+            share_prefix_now_ = false;
+            step(nullptr, nullptr);
+        }
         for (int guard = 0; guard < 1000 && seqs_.at(id)->state != SeqState::DONE; ++guard) step(nullptr, nullptr);
         Seq* s = seqs_.at(id).get();
         if (lnf_rows_out)
@@ -1411,7 +983,6 @@ public:
     }
 
 private:
-    static constexpr int kMaxBlocks = 66;         // ceil(1047 / 16)
     static constexpr int kMaxLatRows = 608;
     static constexpr int kMelVocab = 1026;
     static constexpr int kHeadPad = 1088;         // mel_head columns padded to a multiple of 64
@@ -1436,120 +1007,54 @@ private:
         int kind;   // decode profile events: 0..4 = GEMM kind (aur_stats.gemm_kind_*), 5 = paged attention
         int count;  // launches between the two events (decode profile batches; 1 for a vocoder conv)
     };
-    struct LayerW {
-        const float *ln1w, *ln1b, *wqkv, *bqkv, *wproj, *bproj, *ln2w, *ln2b, *wfc, *bfc, *wproj2, *bproj2;
-        const void *sqkv, *sproj, *sfc, *sproj2;    // launch_pack_wsplit copies for the prefill-regime GEMM (the three bf16 planes of the split)
-        const float *tqkv, *tproj, *tfc, *tproj2;   // pack_wt16 copies for the decode-regime GEMM (gemm_rows_kernel); tqkv / tfc
-                                                    // have LayerNorm folded in (launch_fold_ln)
-        const float *qkv_c1, *qkv_c2, *fc_c1, *fc_c2;   // ... with these epilogue vectors
+    struct Linear {   // one entry of kLinears in one layer
+        const float *w, *b;       // the loaded [K][N] matrix (aur_config.gpt_fp16: W'' once ensure_gpt has run) and bias
+        const float *lnw, *lnb;   // gain and shift of the LayerNorm in front of it, or null
+        int K, N;
+        DecodeOperand op;    // decode-regime GEMM (gemm_rows_kernel): packed weights, c1, effective bias (prepare_decode_operand)
+        const void* split;   // prefill-regime GEMM: the three bf16 planes of launch_pack_wsplit (only the split arithmetic uses them)
     };
-    // device-side repack of one [K][N] matrix into the decode GEMM's tile order (done once per load)
-    const float* packed_copy(const float* Wm, int ldw, int K, int N) {
-        packed_.emplace_back(new DevBuf());
-        DevBuf& b = *packed_.back();
-        b.ensure((size_t)K * N * sizeof(float));
-        launch_pack_wt16(Wm, ldw, b.as<float>(), K, N, st_);
-        return b.as<float>();
-    }
-    // pre-split copy of one [K][N] matrix for the prompt-row GEMM (only the split arithmetic uses it)
-    const void* split_copy(const float* Wm, int K, int N) {
-        if (gemm_prec_ != 1 || !gemm_presplit_) return nullptr;
-        packed_.emplace_back(new DevBuf());
-        DevBuf& b = *packed_.back();
-        b.ensure((size_t)3 * K * N * 2);
-        launch_pack_wsplit(Wm, N, b.p, K, N, st_);
-        return b.p;
-    }
-    // LayerNorm-folded packed copy of a [K][N] matrix plus its two epilogue vectors (launch_fold_ln)
-    const float* folded_copy(const float* Wm, const float* gamma, const float* beta, const float* bias, int K, int N,
-                             const float** c1, const float** c2) {
-        fold_scratch_.ensure((size_t)K * N * sizeof(float));
-        packed_.emplace_back(new DevBuf());
-        DevBuf& b = *packed_.back();
-        b.ensure((size_t)K * N * sizeof(float));
-        packed_.emplace_back(new DevBuf());
-        DevBuf& v = *packed_.back();
-        v.ensure((size_t)2 * N * sizeof(float));
-        launch_fold_ln(Wm, N, gamma, beta, bias, fold_scratch_.as<float>(), b.as<float>(), v.as<float>(), v.as<float>() + N, K, N, st_);
-        *c1 = v.as<float>();
-        *c2 = v.as<float>() + N;
-        return b.as<float>();
-    }
-    // aur_config.gpt_fp16: the fp16 packed copy (launch_pack_wt16_f16, or launch_fold_ln_f16 with its epilogue vectors when gamma is
-    // given) of the loaded matrix `name`, which is overwritten with its effective weights W''
-    const float* f16_copy(const std::string& name, const float* gamma, const float* beta, const float* bias, int K, int N,
-                          const float** c1, const float** c2, int* bad) {
-        float* Wm = w_.at(name).d();
-        packed_.emplace_back(new DevBuf());
-        DevBuf& b = *packed_.back();
-        b.ensure((size_t)K * N * 2);
-        if (gamma) {
-            packed_.emplace_back(new DevBuf());
-            DevBuf& v = *packed_.back();
-            v.ensure((size_t)2 * N * sizeof(float));
-            launch_fold_ln_f16(Wm, N, gamma, beta, bias, Wm, b.p, v.as<float>(), v.as<float>() + N, bad, K, N, st_);
-            *c1 = v.as<float>();
-            *c2 = v.as<float>() + N;
-        } else {
-            launch_pack_wt16_f16(Wm, N, nullptr, Wm, b.p, bad, K, N, st_);
-        }
-        return b.as<float>();
-    }
+    enum { kQkv, kProj, kFc, kProj2 };   // indices into kLinears / LayerW::lin, = the GEMM kind of the decode profile
+    struct LayerW {
+        Linear lin[4];
+    };
     void ensure_gpt() {
         if (gpt_ready_) return;
         layers_.clear();
-        const int H = kHidden;
-        for (int i = 0; i < cfg_.n_layer; ++i) {
-            const std::string p = "gpt.h." + std::to_string(i) + ".";
-            LayerW l;
-            l.ln1w = W(p + "ln_1.w", H); l.ln1b = W(p + "ln_1.b", H);
-            l.wqkv = W(p + "attn.c_attn.w", (int64_t)H * 3 * H); l.bqkv = W(p + "attn.c_attn.b", 3 * H);
-            l.wproj = W(p + "attn.c_proj.w", (int64_t)H * H); l.bproj = W(p + "attn.c_proj.b", H);
-            l.ln2w = W(p + "ln_2.w", H); l.ln2b = W(p + "ln_2.b", H);
-            l.wfc = W(p + "mlp.c_fc.w", (int64_t)H * 4 * H); l.bfc = W(p + "mlp.c_fc.b", 4 * H);
-            l.wproj2 = W(p + "mlp.c_proj.w", (int64_t)4 * H * H); l.bproj2 = W(p + "mlp.c_proj.b", H);
-            l.tqkv = l.tproj = l.tfc = l.tproj2 = nullptr;
-            l.sqkv = l.sproj = l.sfc = l.sproj2 = nullptr;
-            l.qkv_c1 = l.qkv_c2 = l.fc_c1 = l.fc_c2 = nullptr;
-            layers_.push_back(l);
-        }
         packed_.clear();
+        const int H = kHidden;
+        // aur_config.gpt_fp16: fp16 decode operands by the rule of launch_pack_wt16_f16; the matrices themselves are replaced by W'' in
+        // place, so the prompt-row GEMMs (their pre-split planes are taken afterwards) and second_pass run on the same effective
+        // weights.  Converting W'' again gives the same bits.
+        DevBuf dbad;   // (never read: check_gpt_f16 has checked before anything is converted)
         if (gpt_f16_) {
-            // fp16 decode copies by the rule of aur_config.gpt_fp16; the matrices themselves are replaced by W'' in place, so the
-            // prompt-row GEMMs below (and second_pass) run on the same effective weights.  Converting W'' again gives the same bits.
             check_gpt_f16();
-            DevBuf dbad;
             dbad.ensure(sizeof(int));
-            for (int i = 0; i < cfg_.n_layer; ++i) {
-                LayerW& l = layers_[i];
-                const std::string p = "gpt.h." + std::to_string(i) + ".";
-                for (auto& m : gpt_f16_mats(p))
-                    if (!m.gamma.empty() && w_.at(m.w).f16_eff && !w_.at(m.gamma).f16_eff)
-                        throw StateError("gpt_fp16: " + m.gamma + " was loaded again after " + m.w + " was converted with the previous "
-                                         "one; load " + m.w + " again as well");
-                l.tqkv = f16_copy(p + "attn.c_attn.w", l.ln1w, l.ln1b, l.bqkv, H, 3 * H, &l.qkv_c1, &l.qkv_c2, dbad.as<int>());
-                l.tproj = f16_copy(p + "attn.c_proj.w", nullptr, nullptr, nullptr, H, H, nullptr, nullptr, dbad.as<int>());
-                l.tfc = f16_copy(p + "mlp.c_fc.w", l.ln2w, l.ln2b, l.bfc, H, 4 * H, &l.fc_c1, &l.fc_c2, dbad.as<int>());
-                l.tproj2 = f16_copy(p + "mlp.c_proj.w", nullptr, nullptr, nullptr, 4 * H, H, nullptr, nullptr, dbad.as<int>());
-                for (auto& m : gpt_f16_mats(p)) {
-                    w_.at(m.w).f16_eff = true;
-                    if (!m.gamma.empty()) w_.at(m.gamma).f16_eff = true;
-                }
-            }
-            HIP_CHECK(hipStreamSynchronize(st_));   // (dbad: checked before the conversion by check_gpt_f16)
         }
-        {
-            for (auto& l : layers_) {
-                if (!gpt_f16_) {
-                    l.tqkv = folded_copy(l.wqkv, l.ln1w, l.ln1b, l.bqkv, H, 3 * H, &l.qkv_c1, &l.qkv_c2);
-                    l.tproj = packed_copy(l.wproj, H, H, H);
-                    l.tfc = folded_copy(l.wfc, l.ln2w, l.ln2b, l.bfc, H, 4 * H, &l.fc_c1, &l.fc_c2);
-                    l.tproj2 = packed_copy(l.wproj2, H, 4 * H, H);
+        for (int i = 0; i < cfg_.n_layer; ++i) {
+            const std::string p = layer_prefix(i);
+            layers_.emplace_back();
+            for (int k = 0; k < 4; ++k) {
+                const LinearSpec& m = kLinears[k];
+                const std::string wn = p + m.name + ".w", gn = m.ln ? p + m.ln + ".w" : "";
+                Linear& L = layers_.back().lin[k];
+                L.K = m.K; L.N = m.N;
+                L.w = W(wn, (int64_t)m.K * m.N); L.b = W(p + m.name + ".b", m.N);
+                L.lnw = m.ln ? W(gn, m.K) : nullptr; L.lnb = m.ln ? W(p + m.ln + ".b", m.K) : nullptr;
+                if (gpt_f16_ && m.ln && w_.at(wn).f16_eff && !w_.at(gn).f16_eff)
+                    throw StateError("gpt_fp16: " + gn + " was loaded again after " + wn + " was converted with the previous "
+                                     "one; load " + wn + " again as well");
+                L.op = prepare_decode_operand(gpt_f16_ ? 2 : gemm_prec_, L.w, m.N, L.lnw, L.lnb, L.b, m.K, m.N, w_.at(wn).d(), dbad.as<int>(),
+                                              fold_scratch_, packed_, st_);
+                if (gpt_f16_) w_.at(wn).f16_eff = true;
+                if (gpt_f16_ && m.ln) w_.at(gn).f16_eff = true;
+                L.split = nullptr;
+                if (gemm_prec_ == 1 && gemm_presplit_) {
+                    packed_.emplace_back(new DevBuf());
+                    packed_.back()->ensure((size_t)3 * m.K * m.N * 2);
+                    launch_pack_wsplit(L.w, m.N, packed_.back()->p, m.K, m.N, st_);
+                    L.split = packed_.back()->p;
                 }
-                l.sqkv = split_copy(l.wqkv, H, 3 * H);
-                l.sproj = split_copy(l.wproj, H, H);
-                l.sfc = split_copy(l.wfc, H, 4 * H);
-                l.sproj2 = split_copy(l.wproj2, 4 * H, H);
             }
         }
         wte_ = W("gpt.wte", (int64_t)kMelVocab * H);
@@ -1558,7 +1063,8 @@ private:
         fnw_ = W("final_norm.w", H); fnb_ = W("final_norm.b", H);
         headT_ = W("mel_head.wT", (int64_t)H * kHeadPad);
         headb_ = W("mel_head.b", kHeadPad);
-        thead_ = packed_copy(headT_, kHeadPad, H, kHeadPad);
+        thead_ = prepare_decode_operand(gemm_prec_, headT_, kHeadPad, nullptr, nullptr, nullptr, H, kHeadPad, nullptr, nullptr, fold_scratch_,
+                                        packed_, st_).Wt;
         HIP_CHECK(hipStreamSynchronize(st_));
         fold_scratch_.release();
         text_emb_ = W("text_emb");
@@ -1597,14 +1103,18 @@ private:
     // stream, K/V pages and latents of the sequences are not touched).  One pair per n_layer launches: the interval is the
     // launch-to-launch period a kernel-trace reports per kernel.  Algorithmic bytes of a GEMM launch: weights once + the activation
     // rows once + the output tile once (the residual epilogue reads and writes it).
-    ConvEvent& prof_event(int kind, double flops, double bytes, int count) {
-        if (n_gemm_events_ == gemm_events_.size()) {
+    // the next event pair of a pool that grows on demand and is reused from the start once its events have been collected
+    static ConvEvent& next_event(std::vector<ConvEvent>& pool, size_t& n_used) {
+        if (n_used == pool.size()) {
             ConvEvent e{};
             HIP_CHECK(hipEventCreate(&e.a));
             HIP_CHECK(hipEventCreate(&e.b));
-            gemm_events_.push_back(e);
+            pool.push_back(e);
         }
-        ConvEvent& ev = gemm_events_[n_gemm_events_++];
+        return pool[n_used++];
+    }
+    ConvEvent& prof_event(int kind, double flops, double bytes, int count) {
+        ConvEvent& ev = next_event(gemm_events_, n_gemm_events_);
         ev.kind = kind;
         ev.flops = flops;
         ev.bytes = bytes;
@@ -1615,26 +1125,25 @@ private:
         return (a.prec == 2 ? 2.0 : 4.0) * a.K * a.N + 4.0 * ((double)a.M * a.K + (double)a.M * a.N * (epi == kEpiResidual ? 2.0 : 1.0));
     }
     // the four GEMM launches of layer l exactly as forward_decode issues them; `redirect` sends every output to the profile scratch
-    GemmRowsArgs decode_gemm_args(RowWs& w, int l, int kind, int M, const int* d_row_slot, bool redirect) {
-        const LayerW& L = layers_[l];
+    GemmRowsArgs decode_gemm_args(RowWs& w, int l, int kind, int M, bool redirect) {
+        const Linear& L = layers_[l].lin[kind];
         const int mtt = w.rows_cap / 16;   // h, att, act are packed rows (pk_off) with this many 16-row tiles
         float* h = w.h.as<float>();
         GemmRowsArgs a{};
         a.M = M; a.prec = gpt_f16_ ? 2 : gemm_prec_; a.xmt = mtt;
         a.ksp_buf = ksp_buf_.as<float>(); a.ksp_cnt = ksp_cnt_.as<unsigned>();
-        if (kind == 0) {
-            a.eps = 1e-5f; a.X = h; a.Wt = L.tqkv; a.N = 3 * kHidden; a.K = kHidden; a.bias = L.qkv_c2;
-            a.ln_c1 = L.qkv_c1; a.stats_in = w.stats.as<float2>(); a.out = redirect ? prof_q_.as<float>() : w.qbuf.as<float>(); a.ldo = kHidden;
+        a.Wt = L.op.Wt; a.N = L.N; a.K = L.K; a.bias = L.op.bias; a.ln_c1 = L.op.c1;
+        if (kind == kQkv) {
+            a.eps = 1e-5f; a.X = h; a.stats_in = w.stats.as<float2>(); a.out = redirect ? prof_q_.as<float>() : w.qbuf.as<float>(); a.ldo = kHidden;
             a.kv_layer = redirect ? prof_kv_.p : kv_layer(l); a.kv_half = kv_half_ ? 1 : 0; a.row_meta = w.row_meta.as<int>();
-        } else if (kind == 1) {
-            a.X = w.att.as<float>(); a.Wt = L.tproj; a.N = kHidden; a.K = kHidden; a.bias = L.bproj;
+        } else if (kind == kProj) {
+            a.X = w.att.as<float>();
             a.out = redirect ? prof_h_.as<float>() : h; a.omt = mtt; a.stats_out = redirect ? prof_stats_.as<float2>() : w.stats.as<float2>();
-        } else if (kind == 2) {
-            a.eps = 1e-5f; a.X = h; a.Wt = L.tfc; a.N = 4 * kHidden; a.K = kHidden; a.bias = L.fc_c2;
-            a.ln_c1 = L.fc_c1; a.stats_in = w.stats.as<float2>(); a.out = redirect ? prof_act_.as<float>() : w.act.as<float>(); a.omt = mtt;
+        } else if (kind == kFc) {
+            a.eps = 1e-5f; a.X = h; a.stats_in = w.stats.as<float2>(); a.out = redirect ? prof_act_.as<float>() : w.act.as<float>(); a.omt = mtt;
             a.gelu_erf = cfg_.gelu_erf ? 1 : 0;
         } else {
-            a.X = w.act.as<float>(); a.Wt = L.tproj2; a.N = kHidden; a.K = 4 * kHidden; a.bias = L.bproj2;
+            a.X = w.act.as<float>();
             a.out = redirect ? prof_h_.as<float>() : h; a.omt = mtt;
             // (ln_f computes its own statistics in final_rows_kernel)
             if (l + 1 < cfg_.n_layer) a.stats_out = redirect ? prof_stats_.as<float2>() : w.stats.as<float2>();
@@ -1648,14 +1157,14 @@ private:
     // One decode step through the blocks: 5 launches per layer (QKV GEMM with LN1 folded and KV page write, attention,
     // proj GEMM + residual, FC GEMM with LN2 folded + gelu, proj2 GEMM + residual), no split-K slabs in HBM.  Leaves the
     // residual stream in w.h (ln_f is applied by final_rows_kernel).
-    void forward_decode(RowWs& w, int M, const int* d_row_slot) {
+    void forward_decode(RowWs& w, int M) {
         const int mtt = w.rows_cap / 16;
         for (int l = 0; l < cfg_.n_layer; ++l) {
             for (int kind = 0; kind < 4; ++kind) {
                 bool ln;
                 GemmRowsEpi epi;
                 decode_gemm_kind(kind, &ln, &epi);
-                launch_gemm_rows(decode_gemm_args(w, l, kind, M, d_row_slot, false), ln, epi, w.st);
+                launch_gemm_rows(decode_gemm_args(w, l, kind, M, false), ln, epi, w.st);
                 if (kind == 0)
                     launch_paged_attention(w.qbuf.as<float>(), kv_layer(l), w.row_meta.as<int>(), kMaxBlocks, w.att.as<float>(), M, w.st, mtt, kv_half_);
             }
@@ -1667,7 +1176,7 @@ private:
         a.out = redirect ? prof_act_.as<float>() : w.P2.as<float>(); a.ldo = kHeadPad;
         return a;
     }
-    void profile_replay(RowWs& w, int M, const int* d_row_slot) {
+    void profile_replay(RowWs& w, int M) {
         const int mtt = w.rows_cap / 16, nl = cfg_.n_layer;
         // (the residual replays READ their output scratch -- out += ... -- so a freshly allocated buffer is defined once)
         auto scratch = [&](DevBuf& buf, size_t n) {
@@ -1684,10 +1193,10 @@ private:
             bool ln;
             GemmRowsEpi epi;
             decode_gemm_kind(kind, &ln, &epi);
-            const GemmRowsArgs a0 = decode_gemm_args(w, 0, kind, M, d_row_slot, true);
+            const GemmRowsArgs a0 = decode_gemm_args(w, 0, kind, M, true);
             ConvEvent& ev = prof_event(kind, nl * 2.0 * a0.M * a0.N * a0.K, nl * gemm_alg_bytes(a0, epi), nl);
             HIP_CHECK(hipEventRecord(ev.a, w.st));
-            for (int l = 0; l < nl; ++l) launch_gemm_rows(decode_gemm_args(w, l, kind, M, d_row_slot, true), ln, epi, w.st);
+            for (int l = 0; l < nl; ++l) launch_gemm_rows(decode_gemm_args(w, l, kind, M, true), ln, epi, w.st);
             HIP_CHECK(hipEventRecord(ev.b, w.st));
             if (kind == 0) {   // attention of every layer: the step's q rows against each layer's real K/V pages
                 ConvEvent& ea = prof_event(5, nl * 4.0 * kHidden * step_kv_tokens_, nl * ((kv_half_ ? 4.0 : 8.0) * kHidden * step_kv_tokens_ + 8.0 * kHidden * M), nl);
@@ -1754,17 +1263,9 @@ private:
         }
         n_gemm_events_ = 0;
     }
-    // Query blocks of a batch of prompt rows for launch_prompt_attention: runs of consecutive rows of one slot with positions
-    // ascending by one, cut every 32 rows (from the run's first row: a sequence's blocks do not depend on what else is in the batch).
+    // uploads the query blocks of a batch of prompt rows (prompt_qblocks) for forward_rows and returns their number
     int upload_qblocks(RowWs& w, const std::vector<int>& row_slot, const std::vector<int>& row_pos) {
-        w.h_qblk.clear();
-        const int M = (int)row_slot.size();
-        for (int m = 0; m < M;) {
-            int n = 1;
-            while (m + n < M && n < 32 && row_slot[m + n] == row_slot[m] && row_pos[m + n] == row_pos[m] + n) ++n;
-            w.h_qblk.push_back(make_int2(m, n));
-            m += n;
-        }
+        w.h_qblk = prompt_qblocks(row_slot, row_pos);
         w.i_qblk.ensure(w.h_qblk.size() * sizeof(int2));
         HIP_CHECK(hipMemcpyAsync(w.i_qblk.p, w.h_qblk.data(), w.h_qblk.size() * sizeof(int2), hipMemcpyHostToDevice, w.st));
         return (int)w.h_qblk.size();
@@ -1778,31 +1279,35 @@ private:
         const int* bt = block_tables_.as<int>();
         const int* kvpos = slot_kvpos_.as<int>();
         AUR_REQUIRE(d_row_pos != nullptr, "forward_rows: prompt rows carry explicit positions");
-        launch_rows_ln(nullptr, 0, nullptr, h, layers_[0].ln1w, layers_[0].ln1b, xn, M, 1e-5f, w.st);
+        // P = X @ (one linear of the layer), or what `epi` makes of it
+        auto gemm = [&](const float* X, const Linear& L, const GemmGelu* epi, int slabs) {
+            launch_gemm_tile(X, L.K, L.w, P, M, L.N, L.K, w.st, epi, gemm_prec_, slabs, L.split);
+        };
+        launch_rows_ln(nullptr, 0, nullptr, h, layers_[0].lin[kQkv].lnw, layers_[0].lin[kQkv].lnb, xn, M, 1e-5f, w.st);
         for (int l = 0; l < cfg_.n_layer; ++l) {
-            const LayerW& L = layers_[l];
+            const Linear* L = layers_[l].lin;
             void* kvl = kv_layer(l);
             if (gemm_prec_ == 1) {   // bias, q rows and the K / V page writes in the GEMM's epilogue (27.50 vs 27.62 ms per prefill)
-                GemmGelu qe{L.bqkv, nullptr, 0};
+                GemmGelu qe{L[kQkv].b, nullptr, 0};
                 qe.qbuf = w.qbuf.as<float>(); qe.kv_layer = kvl; qe.row_slot = d_row_slot; qe.row_pos = d_row_pos; qe.block_tables = bt;
                 qe.max_blocks = kMaxBlocks; qe.kv_half = kv_half_ ? 1 : 0;
-                launch_gemm_tile(xn, kHidden, L.wqkv, P, M, 3 * kHidden, kHidden, w.st, &qe, gemm_prec_, 1, L.sqkv);
+                gemm(xn, L[kQkv], &qe, 1);
             } else {
-                launch_gemm_tile(xn, kHidden, L.wqkv, P, M, 3 * kHidden, kHidden, w.st, nullptr, gemm_prec_, 1, L.sqkv);
-                launch_qkv_epilogue(P, 1, L.bqkv, w.qbuf.as<float>(), kvl, d_row_slot, d_row_pos, kvpos, bt, kMaxBlocks, M, w.st, kv_half_);
+                gemm(xn, L[kQkv], nullptr, 1);
+                launch_qkv_epilogue(P, 1, L[kQkv].b, w.qbuf.as<float>(), kvl, d_row_slot, d_row_pos, kvpos, bt, kMaxBlocks, M, w.st, kv_half_);
             }
             launch_prompt_attention(w.qbuf.as<float>(), kvl, w.i_qblk.as<int2>(), n_qblk, d_row_slot, d_row_pos, bt, kMaxBlocks, w.att.as<float>(), w.st, kv_half_);
             // (two K-slabs for this GEMM -- 576 workgroups instead of 288 on 256 CUs: 27.55-27.68 vs 27.82 ms per prefill, four slabs
             // 27.83-27.93: not worth another slab sum)
-            launch_gemm_tile(w.att.as<float>(), kHidden, L.wproj, P, M, kHidden, kHidden, w.st, nullptr, gemm_prec_, 1, L.sproj);
-            launch_rows_ln(P, 1, L.bproj, h, L.ln2w, L.ln2b, xn, M, 1e-5f, w.st);
-            const GemmGelu ge{L.bfc, w.act.as<float>(), cfg_.gelu_erf ? 1 : 0};
-            launch_gemm_tile(xn, kHidden, L.wfc, P, M, 4 * kHidden, kHidden, w.st, &ge, gemm_prec_, 1, L.sfc);
+            gemm(w.att.as<float>(), L[kProj], nullptr, 1);
+            launch_rows_ln(P, 1, L[kProj].b, h, L[kFc].lnw, L[kFc].lnb, xn, M, 1e-5f, w.st);
+            const GemmGelu ge{L[kFc].b, w.act.as<float>(), cfg_.gelu_erf ? 1 : 0};
+            gemm(xn, L[kFc], &ge, 1);
             // K = 4096 against N = 1024: four K-slabs (4x the workgroups of a GEMM that otherwise fills one round of CUs with
             // 256 dependent k-steps); rows_ln sums them in a fixed order
-            launch_gemm_tile(w.act.as<float>(), 4 * kHidden, L.wproj2, P, M, kHidden, 4 * kHidden, w.st, nullptr, gemm_prec_, kProj2Slabs, L.sproj2);
+            gemm(w.act.as<float>(), L[kProj2], nullptr, kProj2Slabs);
             const bool last = (l + 1 == cfg_.n_layer);
-            launch_rows_ln(P, kProj2Slabs, L.bproj2, h, last ? lnfw_ : layers_[l + 1].ln1w, last ? lnfb_ : layers_[l + 1].ln1b,
+            launch_rows_ln(P, kProj2Slabs, L[kProj2].b, h, last ? lnfw_ : layers_[l + 1].lin[kQkv].lnw, last ? lnfb_ : layers_[l + 1].lin[kQkv].lnb,
                            xn, M, 1e-5f, w.st);
         }
     }
@@ -1823,7 +1328,6 @@ private:
         a.force_full_sort = sampler_full_sort_ ? 1 : 0;
         return a;
     }
-    // final_norm -> latent stash -> mel_head GEMM -> fused sampler -> read back tokens/finished flags
     // final_norm -> latent stash -> mel_head GEMM -> fused sampler, in three parts so that the kernel part can be
     // captured in a hipGraph: (1) host->device index uploads, (2) kernels only, (3) token / finished-flag read-back.
     void sample_upload(RowWs& w, const std::vector<int>& sample_row, const std::vector<int>& sample_slot,
@@ -2031,7 +1535,7 @@ private:
         launch_embed_decode(w.i_row_slot.as<int>(), slot_tok_.as<int>(), slot_pos_.as<int>(), wte_, wpe_, w.h.as<float>(), Mk, w.st,
                             w.rows_cap / 16, w.stats.as<float2>(), w.row_meta.as<int>(), slot_kvpos_.as<int>(),
                             block_tables_.as<int>(), kMaxBlocks);
-        forward_decode(w, Mk, w.i_row_slot.as<int>());
+        forward_decode(w, Mk);
         sample_kernels_decode(w, Mk);
     }
     // ---- pipelined decode (default): the step's kernel chain depends only on device-resident state, so step s+1 is
@@ -2080,7 +1584,7 @@ private:
         // step, 1.193 vs 1.194 ms per single-utterance decode step -- the copy is not on the critical path of the pipelined loop)
         sample_readback(w, M, st_, pin_rb_[f.buf].as<int>());
         HIP_CHECK(hipEventRecord(ev_rb_[f.buf], st_));
-        if (f.profiled) profile_replay(w, M, w.i_row_slot.as<int>());   // behind the read-back: the step's tokens do not wait for it
+        if (f.profiled) profile_replay(w, M);   // behind the read-back: the step's tokens do not wait for it
         last_active_ = active;
         return f;
     }
@@ -2141,7 +1645,6 @@ private:
         if (infl_.on) collect_decode_step(infl_);
         retire_finished();
     }
-    void decode(const std::vector<int>& active) { decode_pipelined(active); }
 
     // ------------------------------------------------------------------ vocoder
     void ensure_voc() {
@@ -2168,16 +1671,7 @@ private:
         voc_ready_ = true;
     }
     // the event pair of the next profiled conv launch (nullptr when the engine does not profile)
-    ConvEvent* next_conv_event() {
-        if (!cfg_.profile) return nullptr;
-        if (n_conv_events_ == conv_events_.size()) {
-            ConvEvent e{};
-            HIP_CHECK(hipEventCreate(&e.a));
-            HIP_CHECK(hipEventCreate(&e.b));
-            conv_events_.push_back(e);
-        }
-        return &conv_events_[n_conv_events_++];
-    }
+    ConvEvent* next_conv_event() { return cfg_.profile ? &next_event(conv_events_, n_conv_events_) : nullptr; }
     void conv(ConvArgs& a, int KS, int DIL, double tot_in, double tot_out) {
         ConvEvent* ev = next_conv_event();
         if (ev) {
@@ -2572,33 +2066,7 @@ struct aur_engine {
     aur_engine(const aur_config& c, int dev) : impl(c, dev) {}
 };
 
-template <class F>
-static int guarded(F&& f) {
-    try {
-        f();
-        return AUR_OK;
-    } catch (const aur::InvalidArgument& e) {
-        aur::g_last_error = e.what();
-        return AUR_E_INVALID;
-    } catch (const aur::StateError& e) {
-        aur::g_last_error = e.what();
-        return AUR_E_STATE;
-    } catch (const aur::HipError& e) {
-        aur::g_last_error = e.what();
-        return AUR_E_HIP;
-    } catch (const std::bad_alloc&) {
-        aur::g_last_error = "out of host memory";
-        return AUR_E_NOMEM;
-    } catch (const std::exception& e) {
-        aur::g_last_error = e.what();
-        return AUR_E_HIP;
-    }
-}
-#define CHECK_PTR(p)                                    \
-    if (!(p)) {                                         \
-        aur::g_last_error = "null argument: " #p;       \
-        return AUR_E_INVALID;                           \
-    }
+aur::DbgCtx aur::dbg_ctx(const aur_engine* e) { return e->impl.dbg_ctx(); }
 
 extern "C" {
 
@@ -2725,65 +2193,6 @@ int aur_reset_stats(aur_engine* e) {
 int aur_set_profile(aur_engine* e, int32_t every) {
     CHECK_PTR(e);
     return guarded([&] { e->impl.set_profile(every); });
-}
-int aur_dbg_gemm(aur_engine* e, const float* X, const float* W, float* out, int32_t M, int32_t N, int32_t K) {
-    CHECK_PTR(e);
-    return guarded([&] { e->impl.dbg_gemm(X, W, out, M, N, K); });
-}
-int aur_dbg_gemm_rows(aur_engine* e, const float* X, const float* W, const float* bias, const float* gamma, const float* beta,
-                      float* out, int32_t M, int32_t N, int32_t K, int32_t epi, int32_t ln) {
-    CHECK_PTR(e);
-    CHECK_PTR(X);
-    CHECK_PTR(W);
-    CHECK_PTR(out);
-    return guarded([&] { e->impl.dbg_gemm_rows(X, W, bias, gamma, beta, out, M, N, K, epi, ln != 0); });
-}
-int aur_dbg_gemm_rows_ksplit_stress(aur_engine* e, int32_t M, int32_t iters, int64_t* mismatches_out) {
-    CHECK_PTR(e);
-    CHECK_PTR(mismatches_out);
-    return guarded([&] { *mismatches_out = e->impl.dbg_gemm_rows_ksplit_stress(M, iters); });
-}
-int aur_dbg_lane_xor_selftest(aur_engine* e, int32_t blocks, int64_t* mismatches_out) {
-    CHECK_PTR(e);
-    CHECK_PTR(mismatches_out);
-    return guarded([&] { *mismatches_out = e->impl.dbg_lane_xor_selftest(blocks); });
-}
-int aur_dbg_paged_attention(aur_engine* e, const float* q, const float* k, const float* v, const int32_t* ctx, int32_t M, int32_t ctx_max,
-                            int32_t shared, int32_t kv_half, float* out) {
-    CHECK_PTR(e);
-    CHECK_PTR(q);
-    CHECK_PTR(k);
-    CHECK_PTR(v);
-    CHECK_PTR(ctx);
-    CHECK_PTR(out);
-    return guarded([&] { e->impl.dbg_paged_attention(q, k, v, ctx, M, ctx_max, shared, kv_half != 0, out); });
-}
-int aur_dbg_prompt_attention(aur_engine* e, const float* q, const float* k, const float* v, const int32_t* row_seq, const int32_t* row_pos,
-                             int32_t M, int32_t n_seq, int32_t ctx_max, int32_t shared, int32_t kv_half, float* out) {
-    CHECK_PTR(e);
-    CHECK_PTR(q);
-    CHECK_PTR(k);
-    CHECK_PTR(v);
-    CHECK_PTR(row_seq);
-    CHECK_PTR(row_pos);
-    CHECK_PTR(out);
-    return guarded([&] { e->impl.dbg_prompt_attention(q, k, v, row_seq, row_pos, M, n_seq, ctx_max, shared, kv_half != 0, out); });
-}
-int aur_dbg_layernorm(aur_engine* e, const float* h, const float* gamma, const float* beta, float* out, int32_t M) {
-    CHECK_PTR(e);
-    return guarded([&] { e->impl.dbg_layernorm(h, gamma, beta, out, M); });
-}
-int aur_dbg_conv1d(aur_engine* e, const float* x, const float* wp, const float* bias, const float* res, float* out,
-                   const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout, int32_t L, int32_t KS,
-                   int32_t DIL, int32_t padl, float slope, int32_t ups_s, int32_t ups_p) {
-    CHECK_PTR(e);
-    return guarded([&] { e->impl.dbg_conv1d(x, wp, bias, res, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope, ups_s, ups_p, false); });
-}
-int aur_dbg_conv1d_f16(aur_engine* e, const float* x, const void* wp16, const float* bias, const float* res, float* out,
-                       const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout, int32_t L, int32_t KS,
-                       int32_t DIL, int32_t padl, float slope, int32_t ups_s, int32_t ups_p) {
-    CHECK_PTR(e);
-    return guarded([&] { e->impl.dbg_conv1d(x, wp16, bias, res, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope, ups_s, ups_p, true); });
 }
 int aur_dbg_prefill(aur_engine* e, const int32_t* text_ids, int32_t n_text, uint64_t speaker_key, float repetition_penalty,
                     float* lnf_rows_out, float* logits_out) {
