@@ -86,6 +86,7 @@ EXPORTS = [
     "aur_submit", "aur_step", "aur_poll_finished",
     "aur_release", "aur_cancel", "aur_vocode", "aur_sync", "aur_get_stats", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
     "aur_dbg_paged_attention", "aur_dbg_prompt_attention", "aur_dbg_layernorm", "aur_dbg_conv1d", "aur_dbg_conv1d_f16", "aur_dbg_prefill", "aur_dbg_sample",
+    "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_conv_post",
 ]
 
 _lib = None
@@ -145,6 +146,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                            C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32],
         "aur_dbg_conv1d_f16": [eng, fp, C.c_void_p, fp, fp, fp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32],
+        "aur_dbg_conv1d_args": [eng, C.c_int32, fp, C.c_void_p, fp, fp, ip, C.c_int32, C.c_int32, fp, fp, fp, ip] + [C.c_int32] * 8 +
+                               [C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int64)],
+        "aur_dbg_resblock_round_f16": [eng, fp, C.c_void_p, C.c_void_p, fp, fp, fp, fp, ip] + [C.c_int32] * 6 +
+                                      [C.c_float, C.c_float, C.POINTER(C.c_int64)],
+        "aur_dbg_interp2": [eng, fp, ip, ip] + [C.c_int32] * 6 + [fp, C.c_float, C.POINTER(C.c_int64)],
+        "aur_dbg_conv_post": [eng, fp, fp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, fp, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_prefill": [eng, ip, C.c_int32, C.c_uint64, C.c_float, fp, fp],
         "aur_dbg_sample": [eng, fp, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float,
                            C.POINTER(C.c_uint8), C.c_uint32, C.c_int32, ip],
@@ -540,6 +547,75 @@ class NativeEngine:
         self._check(self.lib.aur_dbg_conv1d_f16(self.h, _fp(x), wp16.ctypes.data_as(C.c_void_p), _fp(bias), _fp(res),
                                                 _fp(out), _ip(lens), B, cin, mtot, cout, L, ks, dil, padl, slope, ups_s, ups_p))
         return out
+
+    # The vocoder's kernels one at a time.  Tensors are plain [B][C][L] float32 arrays (L = max(lens)); outputs start as `sentinel`
+    # unless the caller passes their initial content, and come back with the number of guard words the kernel changed (0 expected).
+    def dbg_conv1d_args(self, variant, x, w, lens, ks, dil, padl, cout, slope=1.0, bias=None, cond=None, cond_row=None, res=None,
+                        mrf=None, out=None, mrf_mode=0, out_slope=1.0, res_unact=1.0, ups_s=0, ups_p=0, sentinel=-777.0):
+        """One ConvArgs launch: variant 0 fp32 kernel (w packed float32), 1 / 2 interleaved halves, register / LDS-DMA staged (w packed
+        float16).  Returns (out, mrf, guard words changed); out is None in modes 1 / 2, mrf in mode 0."""
+        x, lens = _f32(x), _i32(lens)
+        w = np.ascontiguousarray(w, dtype=np.float32 if variant == 0 else np.float16)
+        B, cin, L = x.shape
+        mtot = w.size // (cin * ks)
+        shape = (B, cout, L * max(1, ups_s))
+        bias = None if bias is None else _f32(bias)
+        res = None if res is None else _f32(res)
+        cond = None if cond is None else _f32(cond)
+        cond_row = None if cond_row is None else _i32(cond_row)
+        cond_rows, cond_stride = cond.shape if cond is not None else (0, 0)
+        if mrf_mode != 0:
+            mrf = np.full(shape, sentinel, dtype=np.float32) if mrf is None else _f32(mrf).copy()
+        if mrf_mode in (0, 3):
+            out = np.full(shape, sentinel, dtype=np.float32) if out is None else _f32(out).copy()
+        assert (res is None or res.shape == shape) and (mrf is None or mrf.shape == shape) and (out is None or out.shape == shape)
+        bad = C.c_int64(-1)
+        self._check(self.lib.aur_dbg_conv1d_args(self.h, variant, _fp(x), w.ctypes.data_as(C.c_void_p), _fp(bias), _fp(cond), _ip(cond_row),
+                                                 cond_rows, cond_stride, _fp(res), _fp(mrf), _fp(out), _ip(lens), B, cin, mtot, cout, L, ks,
+                                                 dil, padl, slope, ups_s, ups_p, mrf_mode, out_slope, res_unact, sentinel, C.byref(bad)))
+        return out, mrf, int(bad.value)
+
+    def dbg_resblock_round_f16(self, y, w1, w2, b1, b2, lens, ks, dil, mrf_mode=0, e_slope=0.1, mrf=None, out=None, sentinel=-777.0):
+        """One fused ResBlock round on the activated stream y [B][C][L]; w1 / w2 packed float16.  Returns (out, mrf, guard words
+        changed) as dbg_conv1d_args: out is None in modes 1 / 2, mrf in mode 0.  out=y hands the launcher one tensor for both (it
+        refuses)."""
+        alias = out is y
+        y, lens, b1, b2 = _f32(y), _i32(lens), _f32(b1), _f32(b2)
+        w1, w2 = np.ascontiguousarray(w1, dtype=np.float16), np.ascontiguousarray(w2, dtype=np.float16)
+        B, ch, L = y.shape
+        if mrf_mode != 0:
+            mrf = np.full(y.shape, sentinel, dtype=np.float32) if mrf is None else _f32(mrf).copy()
+        if alias:
+            out = y
+        elif mrf_mode in (0, 3):
+            out = np.full(y.shape, sentinel, dtype=np.float32) if out is None else _f32(out).copy()
+        bad = C.c_int64(-1)
+        self._check(self.lib.aur_dbg_resblock_round_f16(self.h, _fp(y), w1.ctypes.data_as(C.c_void_p), w2.ctypes.data_as(C.c_void_p), _fp(b1),
+                                                        _fp(b2), _fp(mrf), _fp(out), _ip(lens), B, ch, L, ks, dil, mrf_mode, e_slope, sentinel,
+                                                        C.byref(bad)))
+        return out, mrf, int(bad.value)
+
+    def dbg_interp2(self, lat, lat_row, n_lat, frames, out_f16=False, sentinel=-777.0):
+        """The two chained interpolations: lat [R][n_max][C], utterance b blends n_lat[b] rows of lat[lat_row[b]]; frames = the longest
+        utterance's vocoder frames (the row stride of z).  Returns (z [B][C][frames], guard words changed)."""
+        lat, n_lat = _f32(lat), _i32(n_lat)
+        lat_row = None if lat_row is None else _i32(lat_row)
+        R, n_max, ch = lat.shape
+        z = np.full((len(n_lat), ch, frames), sentinel, dtype=np.float32)
+        bad = C.c_int64(-1)
+        self._check(self.lib.aur_dbg_interp2(self.h, _fp(lat), _ip(lat_row), _ip(n_lat), R, n_max, len(n_lat), ch, frames, int(bool(out_f16)),
+                                             _fp(z), sentinel, C.byref(bad)))
+        return z, int(bad.value)
+
+    def dbg_conv_post(self, x, w, lens, slope=0.01, x_f16_act=False, sentinel=-777.0):
+        """conv_post + tanh on x [B][Cin][L], w [Cin][7].  Returns (wav [B][L], guard words changed)."""
+        x, w, lens = _f32(x), _f32(w), _i32(lens)
+        B, cin, L = x.shape
+        wav = np.full((B, L), sentinel, dtype=np.float32)
+        bad = C.c_int64(-1)
+        self._check(self.lib.aur_dbg_conv_post(self.h, _fp(x), _fp(w), _ip(lens), B, cin, L, slope, int(bool(x_f16_act)), _fp(wav), sentinel,
+                                               C.byref(bad)))
+        return wav, int(bad.value)
 
     def dbg_prefill(self, text_ids, speaker_key: int, repetition_penalty: float = 1.0):
         ids = _i32(list(text_ids))

@@ -1,8 +1,9 @@
 // Kernel test harness: the aur_dbg_* entry points of include/auralis_amd.h that run ONE kernel on host arrays (tests/test_gpu_kernels.py,
-// test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and the K-split scratch (DbgCtx)
-// and nothing else; aur_dbg_prefill and aur_dbg_sample drive real engine state and live in engine.hip.
+// test_gpu_vocoder_kernels.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
+// the K-split scratch (DbgCtx) and nothing else; aur_dbg_prefill and aur_dbg_sample drive real engine state and live in engine.hip.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "abi_internal.h"
 #include "gpt_host.h"
@@ -100,6 +101,70 @@ static void dbg_conv1d(const aur_engine* e, const float* x, const void* wp, cons
     else
         launch_conv1d(a, KS, DIL, c.st);
     download(out, dout, n_out, c.st);
+}
+
+// ---- the vocoder's kernels on host arrays [B][C][L] (aur_dbg_conv1d_args, _resblock_round_f16, _interp2, _conv_post) ----
+constexpr size_t kGuardBytes = 4096;
+
+// [B][C][L] floats -> interleaved halves [B][C/16][L][16] (ConvArgs) and back
+static std::vector<_Float16> to_halves(const float* src, int B, int C, long L) {
+    std::vector<_Float16> h((size_t)B * C * L);
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < C; ++c)
+            for (long t = 0; t < L; ++t) h[(((size_t)b * (C / 16) + c / 16) * L + t) * 16 + c % 16] = (_Float16)src[((size_t)b * C + c) * L + t];
+    return h;
+}
+static void from_halves(const _Float16* h, float* dst, int B, int C, long L) {
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < C; ++c)
+            for (long t = 0; t < L; ++t) dst[((size_t)b * C + c) * L + t] = (float)h[(((size_t)b * (C / 16) + c / 16) * L + t) * 16 + c % 16];
+}
+
+// A device tensor [B][C][L] (floats, or interleaved halves) between two guards of kGuardBytes that hold `guard`
+struct GuardedBuf {
+    DevBuf d;
+    int B = 0, C = 0;
+    long L = 0;
+    bool half = false;
+    float guard = 0.f;
+    size_t data_bytes() const { return (size_t)B * C * L * (half ? 2 : 4); }
+    void* data() const { return d.as<char>() + kGuardBytes; }
+    template <class T>
+    void put(const std::vector<T>& body) {   // guard | body | guard
+        std::vector<T> img(2 * kGuardBytes / sizeof(T) + body.size(), (T)guard);
+        std::copy(body.begin(), body.end(), img.begin() + kGuardBytes / sizeof(T));
+        d.upload(img);
+    }
+    void upload(const float* host, int B_, int C_, long L_, bool half_, float guard_) {
+        B = B_; C = C_; L = L_; half = half_; guard = guard_;
+        AUR_REQUIRE(!half || C % 16 == 0, "dbg: interleaved halves need whole 16-channel chunks");
+        if (half) put(to_halves(host, B, C, L));
+        else put(std::vector<float>(host, host + (size_t)B * C * L));
+    }
+    // the tensor back into `host`; returns the 32-bit guard words that changed
+    template <class T>
+    long long get(float* host) {
+        const size_t ng = kGuardBytes / sizeof(T), n = (size_t)B * C * L;
+        std::vector<T> img(2 * ng + n);
+        HIP_CHECK(hipMemcpy(img.data(), d.p, img.size() * sizeof(T), hipMemcpyDeviceToHost));
+        std::vector<T> ref(ng, (T)guard);
+        long long bad = 0;
+        for (const T* g : {img.data(), img.data() + ng + n})
+            for (size_t i = 0; i < kGuardBytes; i += 4) bad += std::memcmp((const char*)g + i, (const char*)ref.data() + i, 4) != 0;
+        if constexpr (std::is_same<T, float>::value) std::copy(img.begin() + ng, img.begin() + ng + n, host);
+        else from_halves(img.data() + ng, host, B, C, L);
+        return bad;
+    }
+    long long download(float* host, hipStream_t st) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        return half ? get<_Float16>(host) : get<float>(host);
+    }
+};
+
+static void check_lens(const int* lens, int B, int L, const char* what) {
+    AUR_REQUIRE(B >= 1 && L >= 1, what);
+    for (int b = 0; b < B; ++b) AUR_REQUIRE(lens[b] >= 1 && lens[b] <= L, what);
+    AUR_REQUIRE(*std::max_element(lens, lens + B) == L, what);   // the row stride is the longest utterance, as in the engine
 }
 
 }  // namespace aur
@@ -360,6 +425,207 @@ int aur_dbg_conv1d_f16(aur_engine* e, const float* x, const void* wp16, const fl
                        int32_t DIL, int32_t padl, float slope, int32_t ups_s, int32_t ups_p) {
     CHECK_PTR(e);
     return guarded([&] { dbg_conv1d(e, x, wp16, bias, res, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope, ups_s, ups_p, true); });
+}
+int aur_dbg_conv1d_args(aur_engine* e, int32_t variant, const float* x, const void* w, const float* bias, const float* cond,
+                        const int32_t* cond_row, int32_t cond_rows, int32_t cond_stride, const float* res, float* mrf, float* out,
+                        const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout, int32_t L, int32_t KS, int32_t DIL,
+                        int32_t padl, float slope, int32_t ups_s, int32_t ups_p, int32_t mrf_mode, float out_slope, float res_unact,
+                        float guard_value, int64_t* guard_changed) {
+    CHECK_PTR(e);
+    CHECK_PTR(x);
+    CHECK_PTR(w);
+    CHECK_PTR(lens);
+    CHECK_PTR(guard_changed);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(variant >= 0 && variant <= 2, "dbg_conv1d_args: variant in {0,1,2}");
+        AUR_REQUIRE(mrf_mode >= 0 && mrf_mode <= 3 && Cin >= 1 && Cout >= 1 && Mtot >= 1 && KS >= 1 && ups_s >= 0, "dbg_conv1d_args: shapes");
+        AUR_REQUIRE(Mtot == Cout * std::max(1, ups_s), "dbg_conv1d_args: Mtot = Cout * max(1, ups_s) virtual channels");
+        AUR_REQUIRE(ups_s == 0 || (mrf_mode == 0 && !res), "dbg_conv1d_args: no residual or MRF on a transposed conv");
+        AUR_REQUIRE(mrf_mode == 0 || mrf, "dbg_conv1d_args: the MRF modes need mrf");
+        AUR_REQUIRE((mrf_mode == 1 || mrf_mode == 2) || out, "dbg_conv1d_args: modes 0 and 3 need out");
+        check_lens(lens, B, L, "dbg_conv1d_args: 1 <= lens[b] <= L = max(lens)");
+        if (cond) {
+            AUR_REQUIRE(cond_row && cond_rows >= 1 && cond_stride >= Cout, "dbg_conv1d_args: cond needs cond_row and cond_stride >= Cout");
+            for (int b = 0; b < B; ++b) AUR_REQUIRE(cond_row[b] >= 0 && cond_row[b] < cond_rows, "dbg_conv1d_args: cond_row out of range");
+        }
+        const bool half = variant != 0;
+        // on halves KS == 2 is the transposed convs (out_act_f16 alone): a plain k = 2 conv would read a halves residual as floats
+        AUR_REQUIRE(!half || KS != 2 || ups_s > 0, "dbg_conv1d_args: KS == 2 on interleaved halves is a transposed conv (ups_s > 0)");
+        const long Lout = (long)L * std::max(1, ups_s);
+        DevBuf dx, dw, db, dc, dcr, dr, dl, dz;
+        GuardedBuf gm, go;
+        if (half) {
+            AUR_REQUIRE(Cin % 16 == 0, "dbg_conv1d_args: interleaved halves need whole 16-channel chunks");
+            dx.upload(to_halves(x, B, Cin, L));
+            if (res) {
+                AUR_REQUIRE(Cout % 16 == 0, "dbg_conv1d_args: interleaved halves need whole 16-channel chunks");
+                dr.upload(to_halves(res, B, Cout, Lout));
+            }
+        } else {
+            dx.upload(x, (size_t)B * Cin * L * 4);
+            if (res) dr.upload(res, (size_t)B * Cout * Lout * 4);
+        }
+        dw.upload(w, (size_t)Mtot * Cin * KS * (half ? 2 : 4));
+        dl.upload(lens, (size_t)B * 4);
+        if (bias) db.upload(bias, (size_t)Cout * 4);
+        if (cond) {
+            dc.upload(cond, (size_t)cond_rows * cond_stride * 4);
+            dcr.upload(cond_row, (size_t)B * 4);
+        }
+        ConvArgs a{};
+        a.x = dx.as<float>();
+        a.wp = dw.as<float>();
+        a.wp16 = half ? dw.p : nullptr;
+        a.bias = db.as<float>();
+        a.cond = dc.as<float>(); a.cond_row = dcr.as<int>(); a.cond_stride = cond_stride;
+        a.res = dr.as<float>();
+        a.base_len = dl.as<int>();
+        a.len_mul = 1;
+        a.Cin = Cin; a.Mtot = Mtot; a.Cout = Cout;
+        a.x_stride = L; a.o_stride = Lout;
+        a.x_bstride = (long)Cin * L; a.o_bstride = (long)Cout * Lout;
+        a.padl = padl; a.slope = slope; a.ups_s = ups_s; a.ups_p = ups_p;
+        a.mrf_mode = mrf_mode; a.out_slope = out_slope; a.res_unact = res_unact;
+        a.max_len = L;
+        a.B = B;
+        if (half) {   // the tensor flags as run_vocoder sets them in fp16 mode
+            a.x_f16 = 1;
+            if (KS == 2) {
+                a.out_act_f16 = 1;
+            } else {
+                a.res_f16 = res ? 1 : 0;
+                a.mrf_f16 = mrf_mode != 0 ? 1 : 0;
+                a.out_act_f16 = (mrf_mode == 0 || mrf_mode == 3) ? 1 : 0;
+            }
+            if (variant == 2) {
+                dz.zeros(256, c.st);
+                a.zeros = dz.p;
+            }
+        }
+        if (mrf_mode != 0) {
+            gm.upload(mrf, B, Cout, Lout, half && a.mrf_f16, guard_value);
+            a.mrf = reinterpret_cast<float*>(gm.data());
+        }
+        if (mrf_mode == 0 || mrf_mode == 3) {
+            go.upload(out, B, Cout, Lout, half && a.out_act_f16, guard_value);
+            a.out = reinterpret_cast<float*>(go.data());
+        }
+        if (half)
+            launch_conv1d_f16(a, KS, DIL, c.st);
+        else
+            launch_conv1d(a, KS, DIL, c.st);
+        long long bad = 0;
+        if (mrf_mode != 0) bad += gm.download(mrf, c.st);
+        if (mrf_mode == 0 || mrf_mode == 3) bad += go.download(out, c.st);
+        *guard_changed = bad;
+    });
+}
+int aur_dbg_resblock_round_f16(aur_engine* e, const float* y, const void* w1, const void* w2, const float* b1, const float* b2,
+                               float* mrf, float* out, const int32_t* lens, int32_t B, int32_t C, int32_t L, int32_t KS, int32_t DIL,
+                               int32_t mrf_mode, float e_slope, float guard_value, int64_t* guard_changed) {
+    CHECK_PTR(e);
+    CHECK_PTR(y);
+    CHECK_PTR(w1);
+    CHECK_PTR(w2);
+    CHECK_PTR(b1);
+    CHECK_PTR(b2);
+    CHECK_PTR(lens);
+    CHECK_PTR(guard_changed);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE((C == 64 || C == 32) && KS >= 1 && mrf_mode >= 0 && mrf_mode <= 3, "dbg_resblock_round: 64 or 32 channels, mode 0..3");
+        AUR_REQUIRE(mrf_mode == 0 || mrf, "dbg_resblock_round: the MRF modes need mrf");
+        AUR_REQUIRE((mrf_mode == 1 || mrf_mode == 2) || out, "dbg_resblock_round: modes 0 and 3 need out");
+        check_lens(lens, B, L, "dbg_resblock_round: 1 <= lens[b] <= L = max(lens)");
+        const size_t wbytes = (size_t)C * C * KS * 2;
+        DevBuf dw1, dw2, db1, db2, dl, dz;
+        GuardedBuf gy, gm, go;   // y between guards too: with out == y it is the output tensor the launcher is handed
+        gy.upload(y, B, C, L, true, guard_value);
+        dw1.upload(w1, wbytes);
+        dw2.upload(w2, wbytes);
+        db1.upload(b1, (size_t)C * 4);
+        db2.upload(b2, (size_t)C * 4);
+        dl.upload(lens, (size_t)B * 4);
+        dz.zeros(256, c.st);
+        RoundArgs a{};
+        a.y = gy.data();
+        a.w1 = dw1.p; a.w2 = dw2.p; a.b1 = db1.as<float>(); a.b2 = db2.as<float>();
+        a.base_len = dl.as<int>(); a.len_mul = 1;
+        a.stride = L; a.bstride = (long)C * L;
+        a.C = C; a.mrf_mode = mrf_mode; a.e_slope = e_slope;
+        a.B = B; a.max_len = L;
+        a.zeros = dz.p;
+        const bool has_out = mrf_mode == 0 || mrf_mode == 3, aliased = has_out && out == y;
+        if (mrf_mode != 0) {
+            gm.upload(mrf, B, C, L, true, guard_value);
+            a.mrf = gm.data();
+        }
+        if (has_out && !aliased) go.upload(out, B, C, L, true, guard_value);
+        if (has_out) (mrf_mode == 0 ? a.out : a.e_out) = aliased ? gy.data() : go.data();
+        launch_resblock_round_f16(a, KS, DIL, c.st);
+        long long bad = 0;
+        if (mrf_mode != 0) bad += gm.download(mrf, c.st);
+        if (has_out) bad += (aliased ? gy : go).download(out, c.st);
+        *guard_changed = bad;
+    });
+}
+int aur_dbg_interp2(aur_engine* e, const float* lat, const int32_t* lat_row, const int32_t* n_lat, int32_t R, int32_t n_max, int32_t B,
+                    int32_t C, int32_t Lz, int32_t out_f16, float* z, float guard_value, int64_t* guard_changed) {
+    CHECK_PTR(e);
+    CHECK_PTR(lat);
+    CHECK_PTR(n_lat);
+    CHECK_PTR(z);
+    CHECK_PTR(guard_changed);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(R >= 1 && n_max >= 1 && B >= 1 && C >= 8 && C % 8 == 0, "dbg_interp2: shapes (channels in whole groups of 8)");
+        std::vector<int> len(B);
+        for (int b = 0; b < B; ++b) {
+            AUR_REQUIRE(n_lat[b] >= 1 && n_lat[b] <= n_max, "dbg_interp2: 1 <= n_lat[b] <= n_max");
+            AUR_REQUIRE(lat_row ? (lat_row[b] >= 0 && lat_row[b] < R) : b < R, "dbg_interp2: lat_row out of range");
+            len[b] = frames_for(n_lat[b]);
+        }
+        check_lens(len.data(), B, Lz, "dbg_interp2: Lz = frames_for(max n_lat)");
+        DevBuf dlat, drow, dn, dl;
+        GuardedBuf gz;
+        dlat.upload(lat, (size_t)R * n_max * C * 4);
+        if (lat_row) drow.upload(lat_row, (size_t)B * 4);
+        dn.upload(n_lat, (size_t)B * 4);
+        dl.upload(len);
+        gz.upload(z, B, C, Lz, out_f16 != 0, guard_value);
+        launch_interp2(dlat.as<float>(), (long)n_max * C, drow.as<int>(), dn.as<int>(), dl.as<int>(), reinterpret_cast<float*>(gz.data()), Lz,
+                       (long)C * Lz, C, B, Lz, c.st, out_f16 != 0);
+        *guard_changed = gz.download(z, c.st);
+    });
+}
+int aur_dbg_conv_post(aur_engine* e, const float* x, const float* w, const int32_t* lens, int32_t B, int32_t Cin, int32_t L, float slope,
+                      int32_t x_f16_act, float* wav, float guard_value, int64_t* guard_changed) {
+    CHECK_PTR(e);
+    CHECK_PTR(x);
+    CHECK_PTR(w);
+    CHECK_PTR(lens);
+    CHECK_PTR(wav);
+    CHECK_PTR(guard_changed);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(Cin >= 1, "dbg_conv_post: shapes");
+        check_lens(lens, B, L, "dbg_conv_post: 1 <= lens[b] <= L = max(lens)");
+        DevBuf dx, dw, dl;
+        GuardedBuf gw;
+        if (x_f16_act) {
+            AUR_REQUIRE(Cin % 16 == 0, "dbg_conv_post: interleaved halves need whole 16-channel chunks");
+            dx.upload(to_halves(x, B, Cin, L));
+        } else {
+            dx.upload(x, (size_t)B * Cin * L * 4);
+        }
+        dw.upload(w, (size_t)Cin * 7 * 4);
+        dl.upload(lens, (size_t)B * 4);
+        gw.upload(wav, B, 1, L, false, guard_value);
+        launch_conv_post(dx.as<float>(), dw.as<float>(), reinterpret_cast<float*>(gw.data()), dl.as<int>(), 1, Cin, L, (long)Cin * L, L, slope,
+                         B, L, c.st, x_f16_act != 0);
+        *guard_changed = gw.download(wav, c.st);
+    });
 }
 
 }  // extern "C"

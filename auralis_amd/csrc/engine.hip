@@ -997,8 +997,6 @@ private:
         return true;
     }
 
-    static int frames_for(int n_lat) { return (int)std::floor((double)(4 * n_lat) * (24000.0 / 22050.0)); }
-
     // ------------------------------------------------------------------ GPT
     struct ConvEvent {
         hipEvent_t a, b;

@@ -1,5 +1,7 @@
 // Launch wrappers for the HiFi-GAN vocoder kernels (vocoder_kernels.hip).
 #pragma once
+#include <cmath>
+
 #include "common.h"
 
 namespace aur {
@@ -87,6 +89,9 @@ struct RoundArgs {
 void launch_resblock_round_f16(const RoundArgs& a, int KS, int DIL, hipStream_t st);
 // same contract on fp16 MFMA inputs (fp32 accumulate, fp32 activations in HBM); uses a.wp16
 void launch_conv1d_f16(const ConvArgs& a, int KS, int DIL, hipStream_t st);
+
+// vocoder frames T' of an utterance of n_lat latent rows: the length the two interpolations below leave (base_len)
+inline int frames_for(int n_lat) { return (int)std::floor((double)(4 * n_lat) * (24000.0 / 22050.0)); }
 
 // z[b][c][j] = interp(interp(latents[b]^T, x4), x24000/22050)[c][j]   (hifigan_decoder.py:787-800)
 // out_f16: z is written as interleaved halves [B][C/16][z_stride][16] = fp16 of the same values (strides in elements), the layout the

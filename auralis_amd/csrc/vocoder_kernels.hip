@@ -1151,6 +1151,10 @@ __global__ __launch_bounds__(256) void interp2_kernel(const float* __restrict__ 
     int i0, i1;
     float lam2;
     lin_src(r2, j, L1, i0, i1, lam2);
+    if (L2 == L1) {   // n_lat <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
+        i0 = i1 = j;
+        lam2 = 0.f;
+    }
     float y[2];
     const int idx[2] = {i0, i1};
 #pragma unroll
@@ -1180,6 +1184,10 @@ __global__ __launch_bounds__(256) void interp2_h_kernel(const float* __restrict_
     int i0, i1;
     float lam2;
     lin_src(r2, j, L1, i0, i1, lam2);
+    if (L2 == L1) {   // n_lat <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
+        i0 = i1 = j;
+        lam2 = 0.f;
+    }
     const int idx[2] = {i0, i1};
     float y[2][8];
 #pragma unroll

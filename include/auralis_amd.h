@@ -318,6 +318,38 @@ int aur_dbg_conv1d(aur_engine* e, const float* x, const float* wp, const float* 
 int aur_dbg_conv1d_f16(aur_engine* e, const float* x, const void* wp16, const float* bias, const float* res,
                        float* out, const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout,
                        int32_t L, int32_t KS, int32_t DIL, int32_t padl, float slope, int32_t ups_s, int32_t ups_p);
+/* ---- the vocoder's kernels one at a time (tests/test_gpu_vocoder_kernels.py) --------------------------
+ * Every tensor is a plain row-major fp32 host array [B][C][L]; where the kernel under test wants the interleaved halves layout
+ * [B][C/16][L][16] the harness converts on the way in and out (exact when the values are fp16-representable).  L, the row stride, is
+ * the longest utterance of `lens` (times ups_s on the output side), as in the engine.  Output tensors are IN/OUT: the caller's content
+ * (a sentinel) is uploaded first, so that what the kernel leaves alone comes back unchanged.  Every device output buffer sits between
+ * two 4 KiB guards filled with `guard_value`; *guard_changed = 32-bit guard words that no longer hold it (0 expected). */
+/* One ConvArgs launch (csrc/vocoder_kernels.h).  variant 0: launch_conv1d, fp32 tensors, w = packed floats [Mtot/MT][Cin][KS][MT].
+ * variant 1 / 2: launch_conv1d_f16 on interleaved halves, w = packed halves [Mtot/MT][Cin/16][KS][MT][16]; 1 = register staging (no
+ * zero page), 2 = with the zero page (the LDS-DMA kernel for 64-row tiles).  Their tensor flags are the engine's: x_f16 always (x is
+ * stored activated; `slope` is ignored), and for KS >= 3 res_f16 with a residual, mrf_f16 with an MRF mode, out_act_f16 in modes 0 and
+ * 3; for KS == 2 (the transposed convs) out_act_f16.  x [B][Cin][L]; res (NULL: none), mrf (modes 1..3), out (modes 0 and 3)
+ * [B][Cout][L * max(1, ups_s)]; cond (NULL: none) [cond_rows][cond_stride], utterance b adds row cond_row[b].  Arguments the
+ * launchers refuse come back as AUR_E_INVALID. */
+int aur_dbg_conv1d_args(aur_engine* e, int32_t variant, const float* x, const void* w, const float* bias, const float* cond,
+                        const int32_t* cond_row, int32_t cond_rows, int32_t cond_stride, const float* res, float* mrf, float* out,
+                        const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout, int32_t L, int32_t KS, int32_t DIL,
+                        int32_t padl, float slope, int32_t ups_s, int32_t ups_p, int32_t mrf_mode, float out_slope, float res_unact,
+                        float guard_value, int64_t* guard_changed);
+/* One fused ResBlock round (RoundArgs, resblock_round_f16_kernel) on the activated stream y [B][C][L], C in {64, 32}; w1 / w2 packed
+ * halves [C/16][KS][C][16], b1 / b2 [C].  mrf_mode 0 writes out; 1 and 2 update mrf; 3 reads mrf and writes out (RoundArgs::e_out,
+ * activated with e_slope).  Passing the array of y as out hands the launcher one device tensor for both, which it refuses. */
+int aur_dbg_resblock_round_f16(aur_engine* e, const float* y, const void* w1, const void* w2, const float* b1, const float* b2,
+                               float* mrf, float* out, const int32_t* lens, int32_t B, int32_t C, int32_t L, int32_t KS, int32_t DIL,
+                               int32_t mrf_mode, float e_slope, float guard_value, int64_t* guard_changed);
+/* The two chained interpolations (interp2_kernel, or interp2_h_kernel when out_f16).  lat [R][n_max][C]; utterance b reads n_lat[b]
+ * rows of lat[lat_row[b]] (lat_row NULL: b) and owns frames_for(n_lat[b]) = floor(4 n * 24000 / 22050) positions of
+ * z [B][C][Lz], Lz = the longest of them. */
+int aur_dbg_interp2(aur_engine* e, const float* lat, const int32_t* lat_row, const int32_t* n_lat, int32_t R, int32_t n_max, int32_t B,
+                    int32_t C, int32_t Lz, int32_t out_f16, float* z, float guard_value, int64_t* guard_changed);
+/* conv_post + tanh (conv_post_kernel): x [B][Cin][L] (x_f16_act: the activated halves form, `slope` unused), w [Cin][7], wav [B][L]. */
+int aur_dbg_conv_post(aur_engine* e, const float* x, const float* w, const int32_t* lens, int32_t B, int32_t Cin, int32_t L, float slope,
+                      int32_t x_f16_act, float* wav, float guard_value, int64_t* guard_changed);
 /* Prefill one prompt and return ln_f rows [n_rows][1024] and the penalised logits [1026] of the last row. */
 int aur_dbg_prefill(aur_engine* e, const int32_t* text_ids, int32_t n_text, uint64_t speaker_key,
                     float repetition_penalty, float* lnf_rows_out, float* logits_out);

@@ -310,6 +310,8 @@ def interp_linear(x: Tensor, scale: float) -> Tensor:
     """
     L = x.shape[-1]
     Lo = int(math.floor(L * scale))
+    if Lo == L:   # torch copies when the length does not change, whatever the scale factor (the second interpolation of <= 2 latents)
+        return x.clone()
     r = np.float32(1.0 / scale)
     j = np.arange(Lo, dtype=np.float32)
     src = np.maximum(r * (j + np.float32(0.5)) - np.float32(0.5), np.float32(0.0)).astype(np.float32)

@@ -29,7 +29,8 @@ def test_oracle_matches_reference_golden(path, xtts_sd):
     assert err < 1e-6, err
 
 
-@pytest.mark.parametrize("L,scale", [(7, 4.0), (280, 4.0), (1120, 24000 / 22050), (20, 24000 / 22050), (1, 4.0)])
+@pytest.mark.parametrize("L,scale", [(7, 4.0), (280, 4.0), (1120, 24000 / 22050), (20, 24000 / 22050), (1, 4.0),
+                                     (4, 24000 / 22050), (8, 24000 / 22050)])   # the last two keep the length: torch copies
 def test_interp_closed_form_matches_torch(L, scale):
     torch.manual_seed(L)
     x = torch.randn(1, 5, L)
