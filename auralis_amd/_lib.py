@@ -44,7 +44,7 @@ class aur_seq_desc(C.Structure):
     _fields_ = [("text_ids", C.POINTER(C.c_int32)), ("n_text", C.c_int32), ("speaker_key", C.c_uint64),
                 ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32),
                 ("repetition_penalty", C.c_float), ("max_tokens", C.c_int32), ("seed", C.c_uint32),
-                ("ignore_stop", C.c_int32), ("priority", C.c_int32)]
+                ("ignore_stop", C.c_int32), ("priority", C.c_int32), ("speed", C.c_float)]
 
 
 class aur_result(C.Structure):
@@ -84,9 +84,9 @@ EXPORTS = [
     "aur_set_conditioning", "aur_set_conditioning_device", "aur_has_conditioning", "aur_compute_conditioning", "aur_comm_unique_id", "aur_comm_init", "aur_broadcast_conditioning",
     "aur_comm_info", "aur_conditioning_checksum",
     "aur_submit", "aur_step", "aur_poll_finished",
-    "aur_release", "aur_cancel", "aur_vocode", "aur_sync", "aur_get_stats", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
+    "aur_release", "aur_cancel", "aur_vocode", "aur_vocode_speed", "aur_sync", "aur_get_stats", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
     "aur_dbg_paged_attention", "aur_dbg_prompt_attention", "aur_dbg_layernorm", "aur_dbg_conv1d", "aur_dbg_conv1d_f16", "aur_dbg_prefill", "aur_dbg_sample",
-    "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_conv_post",
+    "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_interp3", "aur_dbg_conv_post",
 ]
 
 _lib = None
@@ -130,6 +130,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "aur_release": [eng, C.c_uint64],
         "aur_cancel": [eng, C.c_uint64],
         "aur_vocode": [eng, fp, ip, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_int64, ip],
+        "aur_vocode_speed": [eng, fp, ip, fp, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_int64, ip],
         "aur_sync": [eng],
         "aur_get_stats": [eng, C.POINTER(aur_stats)],
         "aur_reset_stats": [eng],
@@ -151,6 +152,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "aur_dbg_resblock_round_f16": [eng, fp, C.c_void_p, C.c_void_p, fp, fp, fp, fp, ip] + [C.c_int32] * 6 +
                                       [C.c_float, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_interp2": [eng, fp, ip, ip] + [C.c_int32] * 6 + [fp, C.c_float, C.POINTER(C.c_int64)],
+        "aur_dbg_interp3": [eng, fp, ip, ip, fp] + [C.c_int32] * 6 + [fp, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_conv_post": [eng, fp, fp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, fp, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_prefill": [eng, ip, C.c_int32, C.c_uint64, C.c_float, fp, fp],
         "aur_dbg_sample": [eng, fp, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float,
@@ -163,6 +165,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if path is None:
         _lib = lib
     return lib
+
+
+def stretched_rows(n_lat: int, speed: float) -> int:
+    """Latent rows after the speed stretch (aur_seq_desc.speed; 0 = unset = 1): L0' = max(1, floor(n_lat * ls)), ls = 1 / speed in
+    double on the float32 value that crosses the ABI -- the rule of csrc/vocoder_kernels.h, for sizing output buffers."""
+    sp = float(np.float32(speed))
+    return max(1, int(np.floor(float(n_lat) * (1.0 if sp == 0.0 else 1.0 / sp))))
+
+
+def samples_for(n_lat: int, speed: float = 0.0) -> int:
+    """Samples the vocoder makes of n_lat latent rows at `speed`: 256 * floor(4 L0' * 24000 / 22050)."""
+    return 256 * int(np.floor(float(4 * stretched_rows(n_lat, speed)) * (24000.0 / 22050.0)))
 
 
 def _f32(a) -> np.ndarray:
@@ -345,10 +359,11 @@ class NativeEngine:
     # -- sequences -------------------------------------------------------------------------------------
     def submit(self, text_ids: Sequence[int], speaker_key: int, temperature: float = 0.75, top_p: float = 0.85,
                top_k: int = 50, repetition_penalty: float = 5.0, max_tokens: int = 605, seed: int = 0,
-               ignore_stop: bool = False, priority: int = 0) -> int:
+               ignore_stop: bool = False, priority: int = 0, speed: float = 0.0) -> int:
+        """`speed`: aur_seq_desc.speed, 0 = unset (= 1.0), else in [0.5, 2.0] (anything else: AurError, AUR_E_INVALID)."""
         ids = _i32(list(text_ids))
         d = aur_seq_desc(_ip(ids), len(ids), speaker_key, temperature, top_p, top_k, repetition_penalty,
-                         max_tokens, seed & 0xFFFFFFFF, int(ignore_stop), int(priority))
+                         max_tokens, seed & 0xFFFFFFFF, int(ignore_stop), int(priority), float(speed))
         sid = C.c_uint64()
         self._check(self.lib.aur_submit(self.h, C.byref(d), C.byref(sid)))
         return sid.value
@@ -434,16 +449,25 @@ class NativeEngine:
             raise RuntimeError("run_until_done: step limit reached")
         return done
 
-    def vocode(self, latents: np.ndarray, n_lat: Optional[Sequence[int]], speaker_key: int) -> List[np.ndarray]:
+    def vocode(self, latents: np.ndarray, n_lat: Optional[Sequence[int]], speaker_key: int,
+               speed: Optional[Sequence[float]] = None) -> List[np.ndarray]:
+        """`speed` (optional, one per utterance, as aur_seq_desc.speed): aur_vocode_speed; None: aur_vocode."""
         lat = _f32(latents)
         if lat.ndim == 2:
             lat = lat[None]
         B, t_max, _ = lat.shape
         nl = _i32(n_lat if n_lat is not None else [t_max] * B)
         stride = int(np.floor(np.floor(t_max * 4.0) * (24000 / 22050))) * 256
-        wav = np.zeros((B, stride), dtype=np.float32)
         ns = np.zeros(B, dtype=np.int32)
-        self._check(self.lib.aur_vocode(self.h, _fp(lat), _ip(nl), B, t_max, speaker_key, _fp(wav), stride, _ip(ns)))
+        if speed is None:
+            wav = np.zeros((B, stride), dtype=np.float32)
+            self._check(self.lib.aur_vocode(self.h, _fp(lat), _ip(nl), B, t_max, speaker_key, _fp(wav), stride, _ip(ns)))
+            return [wav[b, : ns[b]].copy() for b in range(B)]
+        sp = _f32(np.asarray(speed).reshape(B))
+        if np.isfinite(sp).all() and ((sp == 0) | ((sp >= 0.5) & (sp <= 2.0))).all():   # (else the engine refuses; any stride will do)
+            stride = max([stride] + [samples_for(int(n), float(v)) for n, v in zip(nl, sp)])
+        wav = np.zeros((B, stride), dtype=np.float32)
+        self._check(self.lib.aur_vocode_speed(self.h, _fp(lat), _ip(nl), _fp(sp), B, t_max, speaker_key, _fp(wav), stride, _ip(ns)))
         return [wav[b, : ns[b]].copy() for b in range(B)]
 
     def sync(self):
@@ -605,6 +629,19 @@ class NativeEngine:
         bad = C.c_int64(-1)
         self._check(self.lib.aur_dbg_interp2(self.h, _fp(lat), _ip(lat_row), _ip(n_lat), R, n_max, len(n_lat), ch, frames, int(bool(out_f16)),
                                              _fp(z), sentinel, C.byref(bad)))
+        return z, int(bad.value)
+
+    def dbg_interp3(self, lat, lat_row, n_lat, speed, frames, out_f16=False, sentinel=-777.0):
+        """dbg_interp2 with the speed stretch in front: speed [B] as aur_seq_desc.speed; frames = the longest utterance's vocoder frames
+        after its stretch.  Returns (z [B][C][frames], guard words changed)."""
+        lat, n_lat, speed = _f32(lat), _i32(n_lat), _f32(speed)
+        lat_row = None if lat_row is None else _i32(lat_row)
+        R, n_max, ch = lat.shape
+        assert speed.shape == n_lat.shape
+        z = np.full((len(n_lat), ch, frames), sentinel, dtype=np.float32)
+        bad = C.c_int64(-1)
+        self._check(self.lib.aur_dbg_interp3(self.h, _fp(lat), _ip(lat_row), _ip(n_lat), _fp(speed), R, n_max, len(n_lat), ch, frames,
+                                             int(bool(out_f16)), _fp(z), sentinel, C.byref(bad)))
         return z, int(bad.value)
 
     def dbg_conv_post(self, x, w, lens, slope=0.01, x_f16_act=False, sentinel=-777.0):

@@ -1,10 +1,11 @@
 """TTSRequest — same fields, defaults and meaning as the reference dataclass
 (src/auralis/common/definitions/requests.py:134-277).  Fields the reference carries but never consumes on the
 synthesis path (do_sample, length_penalty, sound_norm_refs, load_sample_rate) are kept for
-drop-in compatibility.  `seed` is new surface (per-request noise stream; the reference has none)."""
+drop-in compatibility.  `seed` is new surface (per-request noise stream; the reference has none); so are `priority` and `speed`."""
 from __future__ import annotations
 
 import copy as _copy
+import math
 import uuid
 from dataclasses import dataclass, field
 from typing import AsyncGenerator, Callable, List, Optional, Union
@@ -50,8 +51,19 @@ class TTSRequest:
     # new surface, like `seed`: > 0 marks the request latency-critical -- its FIRST chunk is what a listener waits for -- and is
     # handed to the engine as aur_seq_desc.priority (the reference has no such knob: tests/integration/stream_ttfb.py only measures)
     priority: int = 0
+    # new surface, like `seed` and `priority`: the speaking rate, 0.5 <= speed <= 2.0, handed to the engine as aur_seq_desc.speed for
+    # every chunk of the request -- the GPT latents are stretched along time by 1 / speed ahead of the vocoder (the XTTS
+    # inference(speed=) rule), so pitch and loudness stay and nothing runs on the finished waveform (the reference's only speed
+    # control is TTSOutput.change_speed, a phase vocoder over the audio)
+    speed: float = 1.0
 
     def __post_init__(self):
+        try:
+            ok = math.isfinite(self.speed) and 0.5 <= float(self.speed) <= 2.0
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"speed must be a finite number in [0.5, 2.0], got {self.speed!r}")
         if self.language == "auto" and isinstance(self.text, str) and len(self.text) > 0:
             self.language = get_language(self.text)
         validate_language(self.language)

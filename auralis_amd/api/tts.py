@@ -78,7 +78,9 @@ class TTS:
     # ------------------------------------------------------------------ generation
     @staticmethod
     def split_requests(request: TTSRequest, max_length: int = 100000) -> List[TTSRequest]:
-        """Texts longer than max_length become several requests with fresh ids (core/tts.py:236-255)."""
+        """Texts longer than max_length become several requests with fresh ids (core/tts.py:236-255).  Every field follows the copy
+        (`speed`, the sampling parameters) except `priority`: latency-critical is the head of the text, the part a listener waits for,
+        so only the first request keeps it."""
         if not isinstance(request.text, str) or len(request.text) <= max_length:
             return [request]
         out = []
@@ -86,6 +88,8 @@ class TTS:
             r = request.copy()
             r.text = request.text[i:i + max_length]
             r.request_id = uuid.uuid4().hex
+            if out:
+                r.priority = 0
             out.append(r)
         return out
 

@@ -246,7 +246,9 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
                                      max_tokens=self.gpt_max_audio_tokens, seed=seed,
                                      **({"ignore_stop": True} if self.fixed_length else {}),
                                      # a latency-critical request: its first chunk is the one somebody waits for
-                                     **({"priority": int(request.priority)} if idx == 0 and getattr(request, "priority", 0) > 0 else {}))
+                                     **({"priority": int(request.priority)} if idx == 0 and getattr(request, "priority", 0) > 0 else {}),
+                                     # the speaking rate belongs to the whole request: every chunk carries it
+                                     **({"speed": float(request.speed)} if getattr(request, "speed", 1.0) != 1.0 else {}))
             rid = f"{request.request_id}_{idx}"
             handles.append(ChunkHandle(fut, rid, len(text_ids)))
             ids.append(rid)

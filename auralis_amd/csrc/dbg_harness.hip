@@ -599,6 +599,42 @@ int aur_dbg_interp2(aur_engine* e, const float* lat, const int32_t* lat_row, con
         *guard_changed = gz.download(z, c.st);
     });
 }
+int aur_dbg_interp3(aur_engine* e, const float* lat, const int32_t* lat_row, const int32_t* n_lat, const float* speed, int32_t R,
+                    int32_t n_max, int32_t B, int32_t C, int32_t Lz, int32_t out_f16, float* z, float guard_value, int64_t* guard_changed) {
+    CHECK_PTR(e);
+    CHECK_PTR(lat);
+    CHECK_PTR(n_lat);
+    CHECK_PTR(speed);
+    CHECK_PTR(z);
+    CHECK_PTR(guard_changed);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(R >= 1 && n_max >= 1 && B >= 1 && C >= 8 && C % 8 == 0, "dbg_interp3: shapes (channels in whole groups of 8)");
+        std::vector<int> len(B), l0(B);
+        std::vector<float> r0(B);
+        for (int b = 0; b < B; ++b) {
+            AUR_REQUIRE(n_lat[b] >= 1 && n_lat[b] <= n_max, "dbg_interp3: 1 <= n_lat[b] <= n_max");
+            AUR_REQUIRE(lat_row ? (lat_row[b] >= 0 && lat_row[b] < R) : b < R, "dbg_interp3: lat_row out of range");
+            AUR_REQUIRE(speed_valid(speed[b]), "dbg_interp3: speed 0 (unset) or in [0.5, 2]");
+            l0[b] = stretched_rows(n_lat[b], speed[b]);
+            r0[b] = stretch_ratio(speed[b]);
+            len[b] = frames_for(l0[b]);
+        }
+        check_lens(len.data(), B, Lz, "dbg_interp3: Lz = frames_for(max stretched rows)");
+        DevBuf dlat, drow, dn, dl0, dr0, dl;
+        GuardedBuf gz;
+        dlat.upload(lat, (size_t)R * n_max * C * 4);
+        if (lat_row) drow.upload(lat_row, (size_t)B * 4);
+        dn.upload(n_lat, (size_t)B * 4);
+        dl0.upload(l0);
+        dr0.upload(r0);
+        dl.upload(len);
+        gz.upload(z, B, C, Lz, out_f16 != 0, guard_value);
+        launch_interp3(dlat.as<float>(), (long)n_max * C, drow.as<int>(), dn.as<int>(), dl0.as<int>(), dr0.as<float>(), dl.as<int>(),
+                       reinterpret_cast<float*>(gz.data()), Lz, (long)C * Lz, C, B, Lz, c.st, out_f16 != 0);
+        *guard_changed = gz.download(z, c.st);
+    });
+}
 int aur_dbg_conv_post(aur_engine* e, const float* x, const float* w, const int32_t* lens, int32_t B, int32_t Cin, int32_t L, float slope,
                       int32_t x_f16_act, float* wav, float guard_value, int64_t* guard_changed) {
     CHECK_PTR(e);

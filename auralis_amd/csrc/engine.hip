@@ -533,6 +533,7 @@ public:
         AUR_REQUIRE(n_prompt + d.max_tokens + 4 <= kMaxBlocks * kKvBlockTokens, "prompt + max_tokens exceeds max_model_len");
         AUR_REQUIRE(n_prompt <= cfg_.max_prefill_rows, "prompt longer than max_prefill_rows");
         AUR_REQUIRE(d.repetition_penalty > 0.f, "repetition_penalty > 0");
+        AUR_REQUIRE(speed_valid(d.speed), "speed is 0 (unset) or in [0.5, 2.0]");
         std::lock_guard<std::mutex> lk(mu_);
         {   // reject bad text ids / positions here, not in the middle of a batched prefill
             auto te = w_.find("text_emb"), tp = w_.find("text_pos");
@@ -700,6 +701,7 @@ public:
         voc_block_held_ = false;
         voc_batch_.clear();
         voc_active_ = false;
+        voc_split_rest_ = false;
     }
     void step_locked(int* n_live, int* n_finished_total) {
         use();
@@ -831,10 +833,11 @@ public:
         // nothing waits, so a sequence queued behind an active batch is launched as soon as that batch is done once its hold is up)
         if (voc_queue_.empty()) voc_hold_steps_ = 0;
         else ++voc_hold_steps_;
+        if (voc_queue_.empty()) voc_split_rest_ = false;   // (cancelled meanwhile)
         bool urgent_voc = false;   // an urgent sequence does not wait for company: its batch is whatever has finished with it
         for (Seq* q : voc_queue_) urgent_voc |= q->params.priority > 0;
         if (!voc_active_ && !voc_queue_.empty() &&
-            ((int)voc_queue_.size() >= minb || urgent_voc || (running == 0 && n_wait == 0) || voc_hold_steps_ > kVocHoldSteps)) {
+            ((int)voc_queue_.size() >= minb || urgent_voc || voc_split_rest_ || (running == 0 && n_wait == 0) || voc_hold_steps_ > kVocHoldSteps)) {
             voc_launch();
             voc_hold_steps_ = 0;
         }
@@ -854,7 +857,7 @@ public:
     }
 
     // ------------------------------------------------------------------ standalone vocoder
-    void vocode_host(const float* latents, const int* n_lat, int B, int t_max, uint64_t key, float* wav_out,
+    void vocode_host(const float* latents, const int* n_lat, const float* speed, int B, int t_max, uint64_t key, float* wav_out,
                      int64_t wav_stride, int* n_samples_out) {
         use();
         ensure_voc();
@@ -863,22 +866,25 @@ public:
         AUR_REQUIRE(B >= 1 && t_max >= 1, "B, t_max");
         AUR_REQUIRE(!voc_active_, "vocoder stage busy");
         std::vector<int> nl(n_lat, n_lat + B), cond(B, row);
+        std::vector<float> sp(B, 0.f);
+        if (speed) sp.assign(speed, speed + B);
         int max_samples = 0;
         for (int b = 0; b < B; ++b) {
             AUR_REQUIRE(nl[b] >= 1 && nl[b] <= t_max, "n_lat in [1,t_max]");
-            max_samples = std::max(max_samples, frames_for(nl[b]) * 256);
+            AUR_REQUIRE(speed_valid(sp[b]), "speed is 0 (unset) or in [0.5, 2.0]");
+            max_samples = std::max(max_samples, frames_for(stretched_rows(nl[b], sp[b])) * 256);
         }
         AUR_REQUIRE(wav_stride >= max_samples, "wav_stride too small");
         tmp_lat_.ensure((size_t)B * t_max * kHidden * sizeof(float));
         HIP_CHECK(hipMemcpyAsync(tmp_lat_.p, latents, (size_t)B * t_max * kHidden * sizeof(float),
                                  hipMemcpyHostToDevice, st_voc_));
         tmp_wav_.ensure((size_t)B * max_samples * sizeof(float));
-        run_vocoder(B, nl, tmp_lat_.as<float>(), (long)t_max * kHidden, nullptr, cond, tmp_wav_.as<float>(),
+        run_vocoder(B, nl, sp, tmp_lat_.as<float>(), (long)t_max * kHidden, nullptr, cond, tmp_wav_.as<float>(),
                     max_samples);
         HIP_CHECK(hipStreamSynchronize(st_voc_));
         collect_conv_events();
         for (int b = 0; b < B; ++b) {
-            const int ns = frames_for(nl[b]) * 256;
+            const int ns = frames_for(stretched_rows(nl[b], sp[b])) * 256;
             HIP_CHECK(hipMemcpy(wav_out + (long)b * wav_stride, tmp_wav_.as<float>() + (long)b * max_samples,
                                 (size_t)ns * sizeof(float), hipMemcpyDeviceToHost));
             if (n_samples_out) n_samples_out[b] = ns;
@@ -1727,8 +1733,8 @@ private:
             voc_timed_ = false;
         }
     }
-    // latents: d_lat + lat_row[b]*lat_bstride (lat_row nullable => b); wav: d_wav + b*wav_bstride
-    void run_vocoder(int B, const std::vector<int>& n_lat, const float* d_lat, long lat_bstride,
+    // latents: d_lat + lat_row[b]*lat_bstride (lat_row nullable => b); wav: d_wav + b*wav_bstride; speed[b] as aur_seq_desc.speed
+    void run_vocoder(int B, const std::vector<int>& n_lat, const std::vector<float>& speed, const float* d_lat, long lat_bstride,
                      const std::vector<int>* lat_row, const std::vector<int>& cond_row, float* d_wav, long wav_bstride) {
         ensure_voc();
         if (!ev_va_) {
@@ -1736,14 +1742,20 @@ private:
             HIP_CHECK(hipEventCreate(&ev_vb_));
         }
         std::vector<int>& meta = h_meta_;   // member: the async H2D copy below must not outlive its source
-        meta.assign(4 * (size_t)B, 0);
+        meta.assign(6 * (size_t)B, 0);
         int maxT = 0;
         double totT = 0;
+        bool stretched = false;   // some utterance's speed changes its row count: the three-stage kernel
         for (int b = 0; b < B; ++b) {
+            const int l0 = stretched_rows(n_lat[b], speed[b]);
+            const float r0 = stretch_ratio(speed[b]);
             meta[b] = n_lat[b];
-            meta[B + b] = frames_for(n_lat[b]);
+            meta[B + b] = frames_for(l0);
             meta[2 * B + b] = cond_row[b];
             meta[3 * B + b] = lat_row ? (*lat_row)[b] : b;
+            meta[4 * B + b] = l0;
+            std::memcpy(&meta[5 * B + b], &r0, 4);
+            stretched |= l0 != n_lat[b];
             maxT = std::max(maxT, meta[B + b]);
             totT += meta[B + b];
         }
@@ -1773,7 +1785,12 @@ private:
         // fp16 vocoder: z leaves the interpolation as interleaved halves (what conv_pre's staging rounded it to anyway) and conv_pre
         // runs on the LDS-DMA kernel like every other wide conv (round 5: the register-staged kernel, with 32 spilled VGPRs)
         const bool z_f16 = xt_f16_ && conv_dma_;
-        launch_interp2(d_lat, lat_bstride, d_latrow, d_nlat, d_len, v_z_.as<float>(), (long)T, (long)(1024 * T), 1024, B, maxT, st_voc_, z_f16);
+        // (a batch in which every utterance keeps its rows -- speed 1, or a stretch that floors back to n_lat -- is the two-stage kernel's)
+        if (stretched)
+            launch_interp3(d_lat, lat_bstride, d_latrow, d_nlat, d_nlat + 4 * B, reinterpret_cast<const float*>(d_nlat + 5 * B), d_len,
+                           v_z_.as<float>(), (long)T, (long)(1024 * T), 1024, B, maxT, st_voc_, z_f16);
+        else
+            launch_interp2(d_lat, lat_bstride, d_latrow, d_nlat, d_len, v_z_.as<float>(), (long)T, (long)(1024 * T), 1024, B, maxT, st_voc_, z_f16);
         const float* condt = voc_cond_.as<float>();
         ConvArgs a{};
         a.base_len = d_len; a.B = B; a.cond_row = d_cond; a.cond_stride = kCondStride;
@@ -1864,17 +1881,30 @@ private:
         stats_.vocoder_batches++;
     }
     void voc_launch() {
-        const int B = (int)std::min(voc_queue_.size(), (size_t)cfg_.max_seqs);
+        // The workspace is B x maxT and a slowed utterance is up to twice as long (aur_seq_desc.speed): a pass takes the longest prefix
+        // of the queue with B * maxT <= max_seqs * frames_for(kMaxLatRows), today's worst case; a single utterance is always admissible
+        // and the rest stays queued for the next pass.  (Batch invariance is bitwise, so results do not depend on where the cut falls.)
+        const long cap = (long)cfg_.max_seqs * frames_for(kMaxLatRows);
+        int B = 0, maxT = 0;
+        while (B < (int)std::min(voc_queue_.size(), (size_t)cfg_.max_seqs)) {
+            const Seq* q = voc_queue_[B];
+            const int t = std::max(maxT, frames_for(stretched_rows((int)q->tokens.size(), q->params.speed)));
+            if (B > 0 && (long)(B + 1) * t > cap) break;
+            maxT = t;
+            ++B;
+        }
+        voc_split_rest_ = B < (int)std::min(voc_queue_.size(), (size_t)cfg_.max_seqs);   // the rest goes as soon as the stage is free
         voc_batch_.assign(voc_queue_.begin(), voc_queue_.begin() + B);
         voc_queue_.erase(voc_queue_.begin(), voc_queue_.begin() + B);
         voc_nl_.resize(B);
+        voc_speed_.resize(B);
         std::vector<int> rows(B), cond(B);
-        voc_max_samples_ = 0;
+        voc_max_samples_ = maxT * 256;
         for (int b = 0; b < B; ++b) {
             voc_nl_[b] = (int)voc_batch_[b]->tokens.size();
+            voc_speed_[b] = voc_batch_[b]->params.speed;
             rows[b] = voc_batch_[b]->pool_idx;
             cond[b] = voc_batch_[b]->spk_row;
-            voc_max_samples_ = std::max(voc_max_samples_, frames_for(voc_nl_[b]) * 256);
         }
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -1898,7 +1928,7 @@ private:
         // decode step being over).  hipHostMalloc memory is device-visible and coherent; the event below orders the host's reads.
         float* hw = voc_block_->buf.as<float>();
         float* hl = hw + (size_t)B * voc_max_samples_;
-        run_vocoder(B, voc_nl_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_);
+        run_vocoder(B, voc_nl_, voc_speed_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_);
         for (int b = 0; b < B && cfg_.return_latents; ++b)
             HIP_CHECK(hipMemcpyAsync(hl + (size_t)b * kMaxLatRows * kHidden,
                                      latpool_.as<float>() + (long)rows[b] * kMaxLatRows * kHidden,
@@ -1922,7 +1952,7 @@ private:
         const float* hl = hw + (size_t)B * voc_max_samples_;
         for (int b = 0; b < B; ++b) {
             Seq* s = voc_batch_[b];
-            const int ns = frames_for(voc_nl_[b]) * 256;
+            const int ns = frames_for(stretched_rows(voc_nl_[b], voc_speed_[b])) * 256;
             s->wav = hw + (size_t)b * voc_max_samples_;
             s->n_samples = ns;
             if (cfg_.return_latents) {
@@ -2004,6 +2034,8 @@ private:
     std::deque<Seq*> voc_queue_;
     std::vector<Seq*> voc_batch_;
     std::vector<int> voc_nl_;
+    std::vector<float> voc_speed_;      // aur_seq_desc.speed of the batch's sequences
+    bool voc_split_rest_ = false;       // the last pass left part of the queue behind because of the workspace bound
     int voc_max_samples_ = 0;
     bool voc_active_ = false;
     std::vector<std::unique_ptr<PinBlock>> result_blocks_;   // pool; a block is free when refs == 0 (guarded by mu_)
@@ -2169,11 +2201,15 @@ int aur_cancel(aur_engine* e, uint64_t seq_id) {
 }
 int aur_vocode(aur_engine* e, const float* latents, const int32_t* n_lat, int32_t B, int32_t t_max,
                uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out) {
+    return aur_vocode_speed(e, latents, n_lat, nullptr, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out);
+}
+int aur_vocode_speed(aur_engine* e, const float* latents, const int32_t* n_lat, const float* speed, int32_t B, int32_t t_max,
+                     uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out) {
     CHECK_PTR(e);
     CHECK_PTR(latents);
     CHECK_PTR(n_lat);
     CHECK_PTR(wav_out);
-    return guarded([&] { e->impl.vocode_host(latents, n_lat, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out); });
+    return guarded([&] { e->impl.vocode_host(latents, n_lat, speed, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out); });
 }
 int aur_sync(aur_engine* e) {
     CHECK_PTR(e);

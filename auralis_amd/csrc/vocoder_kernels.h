@@ -1,5 +1,6 @@
 // Launch wrappers for the HiFi-GAN vocoder kernels (vocoder_kernels.hip).
 #pragma once
+#include <algorithm>
 #include <cmath>
 
 #include "common.h"
@@ -98,6 +99,22 @@ inline int frames_for(int n_lat) { return (int)std::floor((double)(4 * n_lat) * 
 // LDS-DMA conv kernel stages from
 void launch_interp2(const float* lat, long lat_bstride, const int* lat_row, const int* n_lat, const int* base_len, float* z,
                     long z_stride, long z_bstride, int C, int B, int max_len, hipStream_t st, bool out_f16 = false);
+
+// Speed control (aur_seq_desc.speed; 0 = unset = 1): the latents are stretched along time by ls = 1 / speed ahead of the two
+// interpolations above, F.interpolate(latents^T, scale_factor=ls, mode="linear").  One definition for the kernel, the host's sizing
+// and the tests: `speed` is the float that crossed the ABI, widened to double.
+inline bool speed_valid(float speed) { return speed == 0.f || (speed >= 0.5f && speed <= 2.0f); }   // false for NaN and infinities
+inline double length_scale(float speed) { return speed == 0.f ? 1.0 : 1.0 / (double)speed; }
+// rows after the stretch, L0' = max(1, floor(n_lat * ls)): the max covers n_lat = 1 at speed > 1 (torch raises; the row is copied)
+inline int stretched_rows(int n_lat, float speed) { return std::max(1, (int)std::floor((double)n_lat * length_scale(speed))); }
+// the scale torch hands its kernel for that stage: float(1 / scale_factor)
+inline float stretch_ratio(float speed) { return (float)(1.0 / length_scale(speed)); }
+
+// The same z on the stretched rows: utterance b reads n_lat[b] rows, l0s[b] = stretched_rows(n_lat[b], speed[b]), r0s[b] =
+// stretch_ratio(speed[b]), base_len[b] = frames_for(l0s[b]).  l0s[b] == n_lat[b] computes bit for bit what launch_interp2 does.
+void launch_interp3(const float* lat, long lat_bstride, const int* lat_row, const int* n_lat, const int* l0s, const float* r0s,
+                    const int* base_len, float* z, long z_stride, long z_bstride, int C, int B, int max_len, hipStream_t st,
+                    bool out_f16 = false);
 
 // wav[b][t] = tanh(sum_{ci,j} w[ci][j] * lrelu(x[b][ci][t+j-3], slope))   (conv_post, no bias)
 void launch_conv_post(const float* x, const float* w, float* wav, const int* base_len, int len_mul, int Cin,

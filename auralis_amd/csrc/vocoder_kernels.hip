@@ -1230,6 +1230,135 @@ void launch_interp2(const float* lat, long lat_bstride, const int* lat_row, cons
 }
 
 // ------------------------------------------------------------------------------------------------
+// Speed control: a third linear interpolation at the head of the chain (aur_seq_desc.speed; the XTTS inference(speed=) rule,
+// F.interpolate(latents^T, scale_factor = 1/speed, mode="linear") ahead of HiFi-GAN).  Utterance b's n_lat[b] rows are stretched to
+// l0s[b] = stretched_rows(n_lat[b], speed[b]) rows with scale r0s[b]; the two stages above then run on l0s[b] rows.  Row s of the
+// stretched sequence, blended from two latent rows; a stretch that keeps the length is the row itself, as in torch (k0 = k1 = s and
+// lam = 0: lerp_f(a, a, 0) returns a bit for bit, so an utterance at speed 1 computes exactly what the interp2 pair computes).
+__device__ __forceinline__ void stretch_src(float r0, int s, int n, int L0, int& k0, int& k1, float& lam) {
+    lin_src(r0, s, n, k0, k1, lam);
+    k0 = min(k0, n - 1);   // (never binds for l0s = floor(n / r0): src < n - 0.5; keeps a caller's inconsistent pair inside the rows)
+    if (L0 == n) {
+        k0 = k1 = s;
+        lam = 0.f;
+    }
+}
+
+// Same thread mapping and stores as interp2_kernel; an output position blends up to eight latent rows, innermost stage first.
+__global__ __launch_bounds__(256) void interp3_kernel(const float* __restrict__ lat, long lat_bstride, const int* __restrict__ lat_row,
+                                                      const int* __restrict__ n_lat, const int* __restrict__ l0s,
+                                                      const float* __restrict__ r0s, const int* __restrict__ base_len,
+                                                      float* __restrict__ z, long z_stride, long z_bstride, int C, float r1, float r2) {
+    const int b = blockIdx.z;
+    const int c = blockIdx.y;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int n = n_lat[b];
+    const int L0 = l0s[b];
+    const int L1 = 4 * L0;
+    const int L2 = base_len[b];
+    if (j >= L2) return;
+    const float r0 = r0s[b];
+    const float* x = lat + (long)(lat_row ? lat_row[b] : b) * lat_bstride + c;   // x[k] = x[k*C]
+    int i0, i1;
+    float lam2;
+    lin_src(r2, j, L1, i0, i1, lam2);
+    if (L2 == L1) {   // L0 <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
+        i0 = i1 = j;
+        lam2 = 0.f;
+    }
+    float y[2];
+    const int idx[2] = {i0, i1};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        int s[2];
+        float lam1;
+        lin_src(r1, idx[u], L0, s[0], s[1], lam1);
+        float w[2];
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            int k0, k1;
+            float lam0;
+            stretch_src(r0, s[v], n, L0, k0, k1, lam0);
+            w[v] = lerp_f(x[(long)k0 * C], x[(long)k1 * C], lam0);
+        }
+        y[u] = lerp_f(w[0], w[1], lam1);
+    }
+    z[(long)b * z_bstride + (long)c * z_stride + j] = lerp_f(y[0], y[1], lam2);
+}
+
+// The interleaved-halves form, as interp2_h_kernel: a thread = eight channels of one position, one 16-byte store.
+__global__ __launch_bounds__(256) void interp3_h_kernel(const float* __restrict__ lat, long lat_bstride, const int* __restrict__ lat_row,
+                                                        const int* __restrict__ n_lat, const int* __restrict__ l0s,
+                                                        const float* __restrict__ r0s, const int* __restrict__ base_len,
+                                                        _Float16* __restrict__ z, long z_stride, long z_bstride, int C, float r1, float r2) {
+    const int b = blockIdx.z;
+    const int c8 = blockIdx.y * 8;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int n = n_lat[b];
+    const int L0 = l0s[b];
+    const int L1 = 4 * L0;
+    const int L2 = base_len[b];
+    if (j >= L2) return;
+    const float r0 = r0s[b];
+    const float* x = lat + (long)(lat_row ? lat_row[b] : b) * lat_bstride + c8;
+    int i0, i1;
+    float lam2;
+    lin_src(r2, j, L1, i0, i1, lam2);
+    if (L2 == L1) {   // L0 <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
+        i0 = i1 = j;
+        lam2 = 0.f;
+    }
+    const int idx[2] = {i0, i1};
+    float y[2][8];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        int s[2];
+        float lam1;
+        lin_src(r1, idx[u], L0, s[0], s[1], lam1);
+        float w[2][8];
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            int k0, k1;
+            float lam0;
+            stretch_src(r0, s[v], n, L0, k0, k1, lam0);
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(x + (long)k0 * C), a1 = *reinterpret_cast<const f32x4*>(x + (long)k0 * C + 4);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(x + (long)k1 * C), b1 = *reinterpret_cast<const f32x4*>(x + (long)k1 * C + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                w[v][e] = lerp_f(a0[e], b0[e], lam0);
+                w[v][e + 4] = lerp_f(a1[e], b1[e], lam0);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) y[u][e] = lerp_f(w[0][e], w[1][e], lam1);
+    }
+    h16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (_Float16)lerp_f(y[0][e], y[1][e], lam2);
+    *reinterpret_cast<h16x8*>(z + (long)b * z_bstride + ((long)(c8 >> 4) * z_stride + j) * 16 + (c8 & 15)) = o;
+}
+
+void launch_interp3(const float* lat, long lat_bstride, const int* lat_row, const int* n_lat, const int* l0s, const float* r0s,
+                    const int* base_len, float* z, long z_stride, long z_bstride, int C, int B, int max_len, hipStream_t st, bool out_f16) {
+    const float r1 = (float)(1.0 / (1024.0 / 256.0));
+    const float r2 = (float)(1.0 / (24000.0 / 22050.0));
+    if (out_f16) {
+        AUR_REQUIRE(C % 16 == 0, "interp3: whole 16-channel chunks for the interleaved fp16 output");
+        dim3 grid((max_len + 255) / 256, C / 8, B);
+        trace_launch("interp3_h_kernel");
+        hipLaunchKernelGGL(interp3_h_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len,
+                           reinterpret_cast<_Float16*>(z), z_stride, z_bstride, C, r1, r2);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    dim3 grid((max_len + 255) / 256, C, B);
+    trace_launch("interp3_kernel");
+    hipLaunchKernelGGL(interp3_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len, z, z_stride,
+                       z_bstride, C, r1, r2);
+    HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
 // conv_post (Cin -> 1, k7, no bias) + tanh.  Cin <= 32.  HBM-bound: reads Cin floats per sample.
 // XH: x is the fp16 vocoder's stage output, already activated, interleaved [C/16][t][16] halves (strides in elements).
 template <bool XH>

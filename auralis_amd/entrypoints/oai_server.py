@@ -166,9 +166,15 @@ async def run_unless_disconnected(http_request: Any, awaitable, poll_s: float = 
             task.cancel()
 
 
-def create_app(tts: Optional[TTS]) -> FastAPI:
+def create_app(tts: Optional[TTS], speed_mode: str = "stretch") -> FastAPI:
+    """`speed_mode`: what the OpenAI `speed` field of /v1/audio/speech does.  "stretch" (default, the reference's behaviour): the
+    finished waveform goes through TTSOutput.change_speed, a phase vocoder on the host.  "latent": the value, clamped to [0.5, 2.0],
+    becomes TTSRequest.speed -- the engine stretches the GPT latents ahead of the vocoder and nothing runs on the waveform."""
+    if speed_mode not in ("stretch", "latent"):
+        raise ValueError(f"speed_mode must be 'stretch' or 'latent', got {speed_mode!r}")
     app = FastAPI(title="auralis_amd TTS server")
     app.state.tts = tts
+    app.state.speed_mode = speed_mode
 
     @app.post("/v1/audio/speech")
     async def generate_audio(request: AudioSpeechGenerationRequest, http_request: Request):
@@ -177,12 +183,15 @@ def create_app(tts: Optional[TTS]) -> FastAPI:
             raise HTTPException(status_code=500, detail="TTS engine not initialized")
         try:
             # the facade owns its own event loop thread: hop over to it and await the result here
-            fut = asyncio.run_coroutine_threadsafe(engine.generate_speech_async(request.to_tts_request()), engine._loop)
+            tts_request = request.to_tts_request()
+            if speed_mode == "latent":
+                tts_request.speed = min(2.0, max(0.5, float(request.speed)))
+            fut = asyncio.run_coroutine_threadsafe(engine.generate_speech_async(tts_request), engine._loop)
             try:
                 output = await run_unless_disconnected(http_request, asyncio.wrap_future(fut))
             except ClientDisconnected:
                 return Response(status_code=499)   # (nobody reads it; nginx's "client closed request")
-            if request.speed != 1.0:
+            if speed_mode == "stretch" and request.speed != 1.0:
                 output = output.change_speed(request.speed)
             data = output.to_bytes(request.response_format)
             return Response(content=data, media_type=_MEDIA[request.response_format])
@@ -278,9 +287,12 @@ def main():
     p.add_argument("--gpt", choices=("fp32", "fp16"), default="fp32",
                    help="fp16: per-layer GPT linears stored as fp16 for the decode GEMMs (aur_config.gpt_fp16); fp32: exact contract")
     p.add_argument("--kv", choices=("fp32", "fp16"), default="fp32", help="fp16: K/V pool stored as fp16 (aur_config.kv_fp16)")
+    p.add_argument("--speed-mode", choices=("stretch", "latent"), default="stretch",
+                   help="the request's `speed`: stretch = phase vocoder over the finished waveform (the reference's behaviour); "
+                        "latent = the engine stretches the GPT latents ahead of the vocoder (TTSRequest.speed, clamped to [0.5, 2.0])")
     a = p.parse_args()
     tts = TTS(scheduler_max_concurrency=a.max_concurrency).from_pretrained(a.model, gpt=a.gpt, kv=a.kv)
-    uvicorn.run(create_app(tts), host=a.host, port=a.port)
+    uvicorn.run(create_app(tts, speed_mode=a.speed_mode), host=a.host, port=a.port)
 
 
 if __name__ == "__main__":

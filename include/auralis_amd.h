@@ -115,6 +115,14 @@ typedef struct aur_seq_desc {
                                  vocoded as soon as its tokens are done, and while it waits or runs the engine admits normal
                                  sequences only up to aur_config.urgent_rows running ones (a decode step's time grows with its
                                  rows).  Results do not depend on it */
+    float speed;              /* speaking rate (new surface, like seed and priority; the reference's counterpart is a phase vocoder over
+                                 the finished waveform, TTSOutput.change_speed).  0 = unset = 1.0; otherwise 0.5 <= speed <= 2.0, anything
+                                 else (or a non-finite value) makes aur_submit fail with AUR_E_INVALID.  The XTTS inference(speed=) rule:
+                                 the GPT latents are linearly interpolated along time by ls = 1 / speed ahead of the vocoder, as
+                                 F.interpolate(latents^T, scale_factor=ls, mode="linear") does -- n rows become
+                                 L0' = max(1, floor(n * ls)) rows (ls = 1.0 / (double)speed), and the vocoder synthesises
+                                 256 * floor(4 L0' * 24000 / 22050) samples at unchanged pitch.  Decoding does not depend on it:
+                                 tokens, aur_result.latents and n_latent_rows are those of speed 1 */
 } aur_seq_desc;
 
 /* Finished sequence.  Pointers stay valid until aur_release(seq_id).  Replaces the RequestOutput consumed at
@@ -263,6 +271,11 @@ int aur_cancel(aur_engine* e, uint64_t seq_id);
  * that bring their own latents: latents [B][t_max][1024], n_lat[B] valid rows each; wav_out [B][wav_stride]. */
 int aur_vocode(aur_engine* e, const float* latents, const int32_t* n_lat, int32_t B, int32_t t_max,
                uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out);
+/* Same with a speaking rate per utterance, speed[B] (aur_seq_desc.speed: 0 = unset = 1.0, else in [0.5, 2.0]); utterance b yields
+ * 256 * floor(4 L0' * 24000 / 22050) samples, L0' = max(1, floor(n_lat[b] / speed[b])), and wav_stride must hold the longest.
+ * speed == NULL is aur_vocode (which forwards here).  New surface; the reference has no counterpart. */
+int aur_vocode_speed(aur_engine* e, const float* latents, const int32_t* n_lat, const float* speed, int32_t B, int32_t t_max,
+                     uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out);
 
 int aur_sync(aur_engine* e);
 int aur_get_stats(aur_engine* e, aur_stats* out);
@@ -347,6 +360,10 @@ int aur_dbg_resblock_round_f16(aur_engine* e, const float* y, const void* w1, co
  * z [B][C][Lz], Lz = the longest of them. */
 int aur_dbg_interp2(aur_engine* e, const float* lat, const int32_t* lat_row, const int32_t* n_lat, int32_t R, int32_t n_max, int32_t B,
                     int32_t C, int32_t Lz, int32_t out_f16, float* z, float guard_value, int64_t* guard_changed);
+/* The same with the speed stretch in front (interp3_kernel / interp3_h_kernel): speed[B] as aur_seq_desc.speed; utterance b owns
+ * frames_for(max(1, floor(n_lat[b] / speed[b]))) positions of z. */
+int aur_dbg_interp3(aur_engine* e, const float* lat, const int32_t* lat_row, const int32_t* n_lat, const float* speed, int32_t R,
+                    int32_t n_max, int32_t B, int32_t C, int32_t Lz, int32_t out_f16, float* z, float guard_value, int64_t* guard_changed);
 /* conv_post + tanh (conv_post_kernel): x [B][Cin][L] (x_f16_act: the activated halves form, `slope` unused), w [Cin][7], wav [B][L]. */
 int aur_dbg_conv_post(aur_engine* e, const float* x, const float* w, const int32_t* lens, int32_t B, int32_t Cin, int32_t L, float slope,
                       int32_t x_f16_act, float* wav, float guard_value, int64_t* guard_changed);
