@@ -87,6 +87,7 @@ EXPORTS = [
     "aur_release", "aur_cancel", "aur_vocode", "aur_vocode_speed", "aur_sync", "aur_get_stats", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
     "aur_dbg_paged_attention", "aur_dbg_prompt_attention", "aur_dbg_layernorm", "aur_dbg_conv1d", "aur_dbg_conv1d_f16", "aur_dbg_prefill", "aur_dbg_sample",
     "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_interp3", "aur_dbg_conv_post",
+    "aur_dbg_gemm_tile", "aur_dbg_qkv_rows", "aur_dbg_rows_ln",
 ]
 
 _lib = None
@@ -136,6 +137,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "aur_reset_stats": [eng],
         "aur_set_profile": [eng, C.c_int32],
         "aur_dbg_gemm": [eng, fp, fp, fp, C.c_int32, C.c_int32, C.c_int32],
+        "aur_dbg_gemm_tile": [eng, fp, C.c_int32, fp, fp, fp] + [C.c_int32] * 7,
+        "aur_dbg_qkv_rows": [eng, fp, fp, fp, ip, ip] + [C.c_int32] * 5 + [fp, fp, fp, C.POINTER(C.c_int64)],
+        "aur_dbg_rows_ln": [eng, fp, C.c_int32, fp, fp, fp, fp, fp, C.c_int32],
         "aur_dbg_gemm_rows": [eng, fp, fp, fp, fp, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32],
         "aur_dbg_gemm_rows_ksplit_stress": [eng, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
         "aur_dbg_lane_xor_selftest": [eng, C.c_int32, C.POINTER(C.c_int64)],
@@ -495,6 +499,43 @@ class NativeEngine:
         out = np.empty((M, N), dtype=np.float32)
         self._check(self.lib.aur_dbg_gemm(self.h, _fp(X), _fp(W), _fp(out), M, N, K))
         return out
+
+    def dbg_gemm_tile(self, X, W, bias=None, slabs: int = 1, epi: int = 0, erf: bool = False, exact: bool = False, K=None) -> np.ndarray:
+        """launch_gemm_tile on X [M][ldx] (K: the leading columns that count, default all) and W [K][N].  epi 0: the raw slabs
+        [slabs][M][N]; epi 1: gelu(X @ W + bias) [M][N], erf or tanh form.  exact: the exact-f32 kernel whatever the engine's mode."""
+        X, W = _f32(X), _f32(W)
+        M, ldx = X.shape
+        K2, N = W.shape
+        K = ldx if K is None else int(K)
+        assert K == K2 and ldx >= K
+        bias = None if bias is None else _f32(bias)
+        out = np.empty((M, N) if epi else (slabs, M, N), dtype=np.float32)
+        self._check(self.lib.aur_dbg_gemm_tile(self.h, _fp(X), ldx, _fp(W), _fp(bias), _fp(out), M, N, K, int(slabs), int(epi),
+                                               int(bool(erf)), int(bool(exact))))
+        return out
+
+    def dbg_qkv_rows(self, X, W, bias, row_seq, row_pos, k, v, fused: bool, kv_half: bool = False):
+        """The prompt-row QKV GEMM + epilogue on a paged pool built from k / v [n_seq][ctx_max][1024] -> (q [M][1024], the pool read
+        back as k, v, stray pool words)."""
+        X, W, bias, row_seq, row_pos = _f32(X), _f32(W), _f32(bias), _i32(row_seq), _i32(row_pos)
+        k, v = _f32(k).copy(), _f32(v).copy()
+        assert X.shape[1] == 1024 and W.shape == (1024, 3072) and k.shape == v.shape and k.shape[2] == 1024
+        q = np.empty((X.shape[0], 1024), dtype=np.float32)
+        stray = C.c_int64(-1)
+        self._check(self.lib.aur_dbg_qkv_rows(self.h, _fp(X), _fp(W), _fp(bias), _ip(row_seq), _ip(row_pos), X.shape[0], k.shape[0], k.shape[1],
+                                              int(bool(fused)), int(bool(kv_half)), _fp(q), _fp(k), _fp(v), C.byref(stray)))
+        return q, k, v, int(stray.value)
+
+    def dbg_rows_ln(self, P, bias, h, gamma, beta):
+        """rows_ln_kernel with slabs P [S][M][1024] (None: S = 0) -> (h + sum_s P[s] + bias, LayerNorm of it)"""
+        h, gamma, beta = _f32(h).copy(), _f32(gamma), _f32(beta)
+        P = None if P is None else _f32(P)
+        bias = None if bias is None else _f32(bias)
+        S = 0 if P is None else P.shape[0]
+        assert P is None or P.shape[1:] == h.shape
+        out = np.empty_like(h)
+        self._check(self.lib.aur_dbg_rows_ln(self.h, _fp(P), S, _fp(bias), _fp(h), _fp(gamma), _fp(beta), _fp(out), h.shape[0]))
+        return h, out
 
     def dbg_gemm_rows(self, X, W, bias=None, gamma=None, beta=None, res=None, epi: int = 0) -> np.ndarray:
         """Decode-regime GEMM: epi 0 bias, 1 bias + gelu_new, 2 res + (X @ W + bias); gamma/beta => LayerNorm prologue."""

@@ -1,5 +1,5 @@
 // Kernel test harness: the aur_dbg_* entry points of include/auralis_amd.h that run ONE kernel on host arrays (tests/test_gpu_kernels.py,
-// test_gpu_vocoder_kernels.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
+// test_gpu_prefill_kernels.py, test_gpu_vocoder_kernels.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
 // the K-split scratch (DbgCtx) and nothing else; aur_dbg_prefill and aur_dbg_sample drive real engine state and live in engine.hip.
 #include <algorithm>
 #include <cstring>
@@ -67,6 +67,39 @@ static void upload_kv_pool(const float* k, const float* v, int n_seq, int ctx_ma
         dpool.upload(std::vector<_Float16>(pool.begin(), pool.end()));
     else
         dpool.upload(pool);
+}
+
+// The pool of upload_kv_pool (shared = 0, every context ctx_max tokens) back into k, v [n_seq][ctx_max][1024], halves widened exactly.
+// Returns the pool words that belong to no token of a context (block 0, the tail of every last block) and are no longer zero.
+static long long download_kv_pool(const DevBuf& dpool, int n_seq, int ctx_max, bool half, const int* table, int stride, float* k, float* v) {
+    const int per_seq = (ctx_max + kKvBlockTokens - 1) / kKvBlockTokens;
+    std::vector<float> pool((size_t)(1 + (long)n_seq * per_seq) * kKvBlockElems);
+    if (half) {
+        std::vector<_Float16> hp(pool.size());
+        HIP_CHECK(hipMemcpy(hp.data(), dpool.p, hp.size() * 2, hipMemcpyDeviceToHost));
+        std::copy(hp.begin(), hp.end(), pool.begin());
+    } else {
+        HIP_CHECK(hipMemcpy(pool.data(), dpool.p, pool.size() * 4, hipMemcpyDeviceToHost));
+    }
+    for (int sq = 0; sq < n_seq; ++sq) {
+        const int* bt = table + (size_t)sq * stride;
+        for (int t = 0; t < ctx_max; ++t)
+            for (int kvi = 0; kvi < 2; ++kvi) {
+                float* row = (kvi ? v : k) + ((size_t)sq * ctx_max + t) * kHidden;
+                for (int h = 0; h < kHeads; ++h) {
+                    float* src = &pool[((((size_t)bt[t / kKvBlockTokens] * 2 + kvi) * kHeads + h) * kKvBlockTokens + t % kKvBlockTokens) * kHeadDim];
+                    std::memcpy(row + h * kHeadDim, src, kHeadDim * sizeof(float));
+                    std::memset(src, 0, kHeadDim * sizeof(float));   // what is left non-zero below belongs to no token
+                }
+            }
+    }
+    long long stray = 0;
+    for (const float& w : pool) {
+        uint32_t bits;
+        std::memcpy(&bits, &w, 4);
+        stray += bits != 0;
+    }
+    return stray;
 }
 
 static void dbg_conv1d(const aur_engine* e, const float* x, const void* wp, const float* bias, const float* res, float* out, const int* lens,
@@ -188,6 +221,119 @@ int aur_dbg_gemm(aur_engine* e, const float* X, const float* W, float* out, int3
         }
         launch_gemm_tile(dx.as<float>(), K, dw.as<float>(), dp.as<float>(), M, N, K, c.st, nullptr, c.prec, 1, ds.p);
         download(out, dp, (size_t)M * N * 4, c.st);
+    });
+}
+// The prefill-regime launcher with everything the engine and cond_net.h vary: ldx, K slabs, the bias + GELU epilogue, exact-f32 on a
+// split-arithmetic engine.  epi 0: out [slabs][M][N] raw slabs; epi 1: out [M][N] = gelu(X @ W + bias).  The output starts as NaN words.
+int aur_dbg_gemm_tile(aur_engine* e, const float* X, int32_t ldx, const float* W, const float* bias, float* out, int32_t M, int32_t N,
+                      int32_t K, int32_t slabs, int32_t epi, int32_t erf, int32_t exact) {
+    CHECK_PTR(e);
+    CHECK_PTR(X);
+    CHECK_PTR(W);
+    CHECK_PTR(out);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(M >= 1 && M <= 8192 && N >= 64 && K >= 16 && ldx >= K, "dbg_gemm_tile: 1..8192 rows, N >= 64, K >= 16, ldx >= K");
+        AUR_REQUIRE(epi == 0 || (epi == 1 && bias && slabs == 1), "dbg_gemm_tile: epi 0, or 1 with a bias and one slab");
+        AUR_REQUIRE(slabs >= 1 && slabs <= 16, "dbg_gemm_tile: 1..16 slabs");
+        const int prec = exact ? 0 : c.prec;
+        const size_t n_out = (size_t)(epi ? 1 : slabs) * M * N * 4;
+        DevBuf dx, dw, db, dp, da, ds;
+        dx.upload(X, (size_t)M * ldx * 4);
+        dw.upload(W, (size_t)K * N * 4);
+        if (bias) db.upload(bias, (size_t)N * 4);
+        DevBuf& dout = epi ? da : dp;
+        dp.ensure((size_t)slabs * M * N * 4);
+        dout.ensure(n_out);
+        HIP_CHECK(hipMemsetAsync(dout.p, 0xFF, n_out, c.st));
+        if (prec == 1 && c.presplit && N % 128 == 0) {   // as aur_dbg_gemm
+            ds.ensure((size_t)3 * K * N * 2);
+            launch_pack_wsplit(dw.as<float>(), N, ds.p, K, N, c.st);
+        }
+        const GemmGelu ge{db.as<float>(), da.as<float>(), erf ? 1 : 0};
+        launch_gemm_tile(dx.as<float>(), ldx, dw.as<float>(), dp.as<float>(), M, N, K, c.st, epi ? &ge : nullptr, prec, slabs, ds.p);
+        download(out, dout, n_out, c.st);
+    });
+}
+// The QKV GEMM of prompt rows with its epilogue (bias, q rows, K / V into the paged pool at (row_seq[m], row_pos[m])): fused != 0 in the
+// GEMM's own epilogue (split arithmetic only), else the plain GEMM and qkv_epilogue_kernel with explicit positions -- forward_rows' two
+// forms.  The pool is built from k_inout / v_inout and read back whole; *stray_out: download_kv_pool.
+int aur_dbg_qkv_rows(aur_engine* e, const float* X, const float* W, const float* bias, const int32_t* row_seq, const int32_t* row_pos,
+                     int32_t M, int32_t n_seq, int32_t ctx_max, int32_t fused, int32_t kv_half, float* q_out, float* k_inout, float* v_inout,
+                     int64_t* stray_out) {
+    CHECK_PTR(e);
+    CHECK_PTR(X);
+    CHECK_PTR(W);
+    CHECK_PTR(bias);
+    CHECK_PTR(row_seq);
+    CHECK_PTR(row_pos);
+    CHECK_PTR(q_out);
+    CHECK_PTR(k_inout);
+    CHECK_PTR(v_inout);
+    CHECK_PTR(stray_out);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(M >= 1 && M <= 8192 && n_seq >= 1 && n_seq <= 64 && ctx_max >= 1 && ctx_max <= kMaxBlocks * kKvBlockTokens,
+                    "dbg_qkv_rows: 1..8192 rows, 1..64 sequences, context 1..1056");
+        AUR_REQUIRE(!fused || c.prec == 1, "dbg_qkv_rows: the fused epilogue needs the split arithmetic");
+        for (int m = 0; m < M; ++m)
+            AUR_REQUIRE(row_seq[m] >= 0 && row_seq[m] < n_seq && row_pos[m] >= 0 && row_pos[m] < ctx_max, "dbg_qkv_rows: row_seq / row_pos out of range");
+        constexpr int N = 3 * kHidden, K = kHidden;
+        std::vector<int> bt((size_t)n_seq * kMaxBlocks, 0);
+        DevBuf dx, dw, db, dpool, dbt, drs, drp, dp, dq, ds;
+        upload_kv_pool(k_inout, v_inout, n_seq, ctx_max, 0, nullptr, kv_half != 0, bt.data(), kMaxBlocks, dpool);
+        dx.upload(X, (size_t)M * K * 4);
+        dw.upload(W, (size_t)K * N * 4);
+        db.upload(bias, (size_t)N * 4);
+        dbt.upload(bt);
+        drs.upload(row_seq, (size_t)M * 4);
+        drp.upload(row_pos, (size_t)M * 4);
+        dp.ensure((size_t)M * N * 4);
+        dq.ensure((size_t)M * kHidden * 4);
+        HIP_CHECK(hipMemsetAsync(dq.p, 0xFF, (size_t)M * kHidden * 4, c.st));
+        if (c.prec == 1 && c.presplit) {   // as aur_dbg_gemm
+            ds.ensure((size_t)3 * K * N * 2);
+            launch_pack_wsplit(dw.as<float>(), N, ds.p, K, N, c.st);
+        }
+        if (fused) {
+            GemmGelu qe{db.as<float>(), nullptr, 0};
+            qe.qbuf = dq.as<float>(); qe.kv_layer = dpool.p; qe.row_slot = drs.as<int>(); qe.row_pos = drp.as<int>(); qe.block_tables = dbt.as<int>();
+            qe.max_blocks = kMaxBlocks; qe.kv_half = kv_half ? 1 : 0;
+            launch_gemm_tile(dx.as<float>(), K, dw.as<float>(), dp.as<float>(), M, N, K, c.st, &qe, c.prec, 1, ds.p);
+        } else {
+            launch_gemm_tile(dx.as<float>(), K, dw.as<float>(), dp.as<float>(), M, N, K, c.st, nullptr, c.prec, 1, ds.p);
+            launch_qkv_epilogue(dp.as<float>(), 1, db.as<float>(), dq.as<float>(), dpool.p, drs.as<int>(), drp.as<int>(), nullptr, dbt.as<int>(),
+                                kMaxBlocks, M, c.st, kv_half != 0);
+        }
+        download(q_out, dq, (size_t)M * kHidden * 4, c.st);
+        *stray_out = download_kv_pool(dpool, n_seq, ctx_max, kv_half != 0, bt.data(), kMaxBlocks, k_inout, v_inout);
+    });
+}
+// rows_ln_kernel with slabs: h[M][1024] += sum of the S slabs P[S][M][1024] + bias (S > 0), out = LayerNorm(h)
+int aur_dbg_rows_ln(aur_engine* e, const float* P, int32_t S, const float* bias, float* h_inout, const float* gamma, const float* beta,
+                    float* out, int32_t M) {
+    CHECK_PTR(e);
+    CHECK_PTR(h_inout);
+    CHECK_PTR(gamma);
+    CHECK_PTR(beta);
+    CHECK_PTR(out);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(M >= 1 && M <= 8192 && S >= 0 && S <= 16, "dbg_rows_ln: 1..8192 rows, 0..16 slabs");
+        AUR_REQUIRE(S == 0 || (P && bias), "dbg_rows_ln: slabs need P and bias");
+        const size_t n = (size_t)M * kHidden * 4;
+        DevBuf dp, dbi, dh, dg, db, dout;
+        if (S > 0) {
+            dp.upload(P, (size_t)S * n);
+            dbi.upload(bias, kHidden * 4);
+        }
+        dh.upload(h_inout, n);
+        dg.upload(gamma, kHidden * 4);
+        db.upload(beta, kHidden * 4);
+        dout.ensure(n);
+        launch_rows_ln(dp.as<float>(), S, dbi.as<float>(), dh.as<float>(), dg.as<float>(), db.as<float>(), dout.as<float>(), M, 1e-5f, c.st);
+        download(out, dout, n, c.st);
+        HIP_CHECK(hipMemcpy(h_inout, dh.p, n, hipMemcpyDeviceToHost));
     });
 }
 // decode-regime GEMM on host data: out = epi(LN?(X) @ W + bias); W is the plain [K][N] matrix, made the kernel's operand on the device

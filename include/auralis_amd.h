@@ -289,6 +289,28 @@ int aur_set_profile(aur_engine* e, int32_t every);
 /* Prefill-regime GEMM (gemm_tile_split_kernel, or gemm_tile_kernel under aur_config.gemm_f32_exact: the kernel every prompt-row
  * linear of vLLM's GPT2Block runs on here, vllm_mm_gpt.py:757-761 at M = prompt rows): out[M][N] = X[M][K] @ W[K][N]. */
 int aur_dbg_gemm(aur_engine* e, const float* X, const float* W, float* out, int32_t M, int32_t N, int32_t K);
+/* The same launcher with everything its callers vary (tests/test_gpu_prefill_kernels.py).  X [M][ldx], ldx >= K; W [K][N]; `slabs`
+ * K slabs of K / slabs consecutive k each.  epi 0: out [slabs][M][N], slab s = X[:, s K/slabs : (s+1) K/slabs] @ the matching rows of W.
+ * epi 1 (one slab, bias [N]): out [M][N] = gelu(X @ W + bias), erf != 0 the erf form (HF "gelu"), else the tanh form ("gelu_new"):
+ * the FC linear and activation of GPT2MLP.  exact != 0 runs gemm_tile_kernel (exact-f32 MFMA) whatever the engine's arithmetic is, as
+ * the speaker-conditioning network does; otherwise the engine's mode, pre-split weight planes included.  The device output starts as
+ * NaN words, so an element no workgroup wrote comes back as NaN. */
+int aur_dbg_gemm_tile(aur_engine* e, const float* X, int32_t ldx, const float* W, const float* bias, float* out, int32_t M, int32_t N,
+                      int32_t K, int32_t slabs, int32_t epi, int32_t erf, int32_t exact);
+/* The QKV linear of prompt rows with its epilogue (GPT2Attention.c_attn and vLLM's K/V cache write, vllm_mm_gpt.py:757-761).
+ * X [M][1024], W [1024][3072], bias [3072]; row m is token row_pos[m] of sequence row_seq[m].  q_out [M][1024] = (X @ W + bias)[:, :1024];
+ * columns 1024..2047 / 2048..3071 of row m go to k_inout / v_inout [n_seq][ctx_max][1024] at [row_seq[m]][row_pos[m]], through a paged
+ * pool (16-token blocks) built from those arrays and read back whole: every other element returns as it came.  kv_half: the fp16 pool
+ * (the arrays' values must be fp16-representable to return unchanged; written values are rounded to nearest).  fused != 0: in the
+ * GEMM's epilogue (AUR_E_INVALID under aur_config.gemm_f32_exact), else the plain GEMM followed by qkv_epilogue_kernel.
+ * *stray_out = pool words that belong to no token of a context (the empty block 0, the tail of a last block) and came back non-zero. */
+int aur_dbg_qkv_rows(aur_engine* e, const float* X, const float* W, const float* bias, const int32_t* row_seq, const int32_t* row_pos,
+                     int32_t M, int32_t n_seq, int32_t ctx_max, int32_t fused, int32_t kv_half, float* q_out, float* k_inout, float* v_inout,
+                     int64_t* stray_out);
+/* rows_ln_kernel with K slabs: h_inout[M][1024] += sum_s P[s] + bias (P [S][M][1024], S in 0..16; S = 0: h unchanged, P and bias
+ * unused), out [M][1024] = LayerNorm(h_inout; gamma, beta, eps 1e-5): the residual add and ln_2 / next ln_1 behind a prompt-row linear. */
+int aur_dbg_rows_ln(aur_engine* e, const float* P, int32_t S, const float* bias, float* h_inout, const float* gamma, const float* beta,
+                    float* out, int32_t M);
 /* Decode-regime GEMM (gemm_rows_kernel: full-K workgroups, fused LayerNorm prologue and bias / gelu / residual epilogue;
  * replaces one GPT2Block linear of vLLM's GPT2Attention / GPT2MLP at M = live sequences, vllm_mm_gpt.py:757-761):
  * out[M][N] = epi(LN?(X[M][K]) @ W[K][N] + bias), epi 0 = bias, 1 = bias + gelu_new, 2 = out += (.. + bias).
