@@ -78,13 +78,18 @@ class aur_stats(C.Structure):
         return out
 
 
+class aur_load(C.Structure):
+    _fields_ = [("waiting", C.c_int32), ("running", C.c_int32), ("vocoding", C.c_int32), ("free_slots", C.c_int32),
+                ("token_budget", C.c_int64)]
+
+
 # every symbol include/auralis_amd.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "aur_last_error", "aur_version", "aur_engine_create", "aur_engine_destroy", "aur_load_weights",
     "aur_set_conditioning", "aur_set_conditioning_device", "aur_has_conditioning", "aur_compute_conditioning", "aur_comm_unique_id", "aur_comm_init", "aur_broadcast_conditioning",
     "aur_comm_info", "aur_conditioning_checksum",
     "aur_submit", "aur_step", "aur_poll_finished",
-    "aur_release", "aur_cancel", "aur_vocode", "aur_vocode_speed", "aur_sync", "aur_get_stats", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
+    "aur_release", "aur_cancel", "aur_vocode", "aur_vocode_speed", "aur_sync", "aur_get_stats", "aur_get_load", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
     "aur_dbg_paged_attention", "aur_dbg_prompt_attention", "aur_dbg_layernorm", "aur_dbg_conv1d", "aur_dbg_conv1d_f16", "aur_dbg_prefill", "aur_dbg_sample",
     "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_interp3", "aur_dbg_conv_post",
     "aur_dbg_gemm_tile", "aur_dbg_qkv_rows", "aur_dbg_rows_ln",
@@ -134,6 +139,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "aur_vocode_speed": [eng, fp, ip, fp, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_int64, ip],
         "aur_sync": [eng],
         "aur_get_stats": [eng, C.POINTER(aur_stats)],
+        "aur_get_load": [eng, C.POINTER(aur_load)],
         "aur_reset_stats": [eng],
         "aur_set_profile": [eng, C.c_int32],
         "aur_dbg_gemm": [eng, fp, fp, fp, C.c_int32, C.c_int32, C.c_int32],
@@ -250,6 +256,7 @@ class NativeEngine:
         self.h = h
         self.max_seqs = max_seqs
         self.n_layer = n_layer
+        self.device = device
         self._lease_lock = threading.Lock()
         self._leases: Dict[int, "weakref.ref"] = {}   # seq_id -> lease handed out by poll(copy=False)
         self._leased_bytes = 0
@@ -481,6 +488,13 @@ class NativeEngine:
         s = aur_stats()
         self._check(self.lib.aur_get_stats(self.h, C.byref(s)))
         return s.as_dict()
+
+    def load(self) -> Dict[str, int]:
+        """aur_get_load: {waiting, running, vocoding, free_slots, token_budget}.  Host only (no HIP call, does not wait for a step):
+        callable from any thread while the driver thread is inside step()."""
+        l = aur_load()
+        self._check(self.lib.aur_get_load(self.h, C.byref(l)))
+        return {n: int(getattr(l, n)) for n, _ in l._fields_}
 
     def reset_stats(self):
         self._check(self.lib.aur_reset_stats(self.h))

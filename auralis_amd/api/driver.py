@@ -40,6 +40,7 @@ class EngineDriver:
         self._urgent = False          # a latency-critical submission (priority > 0) is in the burst: the engine starts at once
         self._burst_loops: set = set()   # event loops that submitted since the engine last went idle
         self._pending: Dict[int, Tuple[asyncio.AbstractEventLoop, asyncio.Future]] = {}
+        self._on_resolved: Dict[int, Any] = {}   # seq id -> callback of a sequence submitted with submit_for (several engines)
         self._lock = threading.Lock()
         self._wake = threading.Event()
         self._stop = False
@@ -54,9 +55,24 @@ class EngineDriver:
         a voice is only pinned from aur_submit on, so between the caller's presence check and this call another request can
         have evicted it; the engine then answers "unknown speaker_key" (AUR_E_INVALID) and the submission is repeated once
         after `reregister()`."""
+        fut = loop.create_future()
+        sid = self.submit_for(fut, loop, reregister=reregister, **seq)
+        # a consumer that walks away (a cancelled task, a closed stream) cancels the future: the engine stops the sequence
+        # instead of decoding it to the end and vocoding it for nobody (aur_cancel).  (Nobody else holds the future yet, and the driver thread
+        # only ever resolves it, so it cannot have been cancelled before the callback is in place.)
+        fut.add_done_callback(lambda f, sid=sid: self._on_done(f, sid))
+        return fut
+
+    def submit_for(self, fut: "asyncio.Future", loop: asyncio.AbstractEventLoop, on_resolved=None, reregister=None, **seq) -> int:
+        """submit() for a future that exists already -- the plugin over several engines creates a chunk's future on the event loop
+        when the request arrives and places the chunk later, possibly from a driver thread, so nothing here touches the future.
+        Returns the engine's sequence id; cancelling is the caller's business (cancel_seq).  `on_resolved` (no arguments) is called
+        on the driver thread, holding no lock of the driver's, once the sequence has resolved -- finished, failed or cancelled --
+        and must not wait for an event loop.  Order: a poll's results are posted to their event loops FIRST, the hooks run after --
+        a finished chunk is not held back by the placement of the next one -- so a consumer can see its result a moment before the
+        hook has run."""
         if self._error is not None:
             raise RuntimeError("engine driver stopped") from self._error
-        fut = loop.create_future()
         with self._lock:
             try:
                 sid = self.engine.submit(**seq)
@@ -66,19 +82,25 @@ class EngineDriver:
                 reregister()
                 sid = self.engine.submit(**seq)
             self._pending[sid] = (loop, fut)
-            # a consumer that walks away (a cancelled task, a closed stream) cancels the future: the engine stops the sequence
-            # instead of decoding it to the end and vocoding it for nobody (aur_cancel)
-            fut.add_done_callback(lambda f, sid=sid: self._on_done(f, sid))
+            if on_resolved is not None:
+                self._on_resolved[sid] = on_resolved
             self._last_submit = time.perf_counter()
             self._burst_loops.add(loop)
             if seq.get("priority", 0) > 0:
                 self._urgent = True
         self._wake.set()
-        return fut
+        return sid
+
+    def cancel_seq(self, sid: int):
+        """Stop a sequence of submit_for whose consumer has gone (what submit() arranges by itself)."""
+        self._cancel_known(sid)
 
     def _on_done(self, fut: "asyncio.Future", sid: int):
         if not fut.cancelled():
             return
+        self._cancel_known(sid)
+
+    def _cancel_known(self, sid: int):
         with self._lock:
             known = self._pending.get(sid) is not None
         cancel = getattr(self.engine, "cancel", None)
@@ -110,6 +132,7 @@ class EngineDriver:
         by_loop: Dict[asyncio.AbstractEventLoop, list] = {}
         with self._lock:
             ents = [(item, self._pending.pop(item["seq_id"], None)) for item in items]
+            hooks = [h for h in (self._on_resolved.pop(item["seq_id"], None) for item in items) if h is not None] if self._on_resolved else ()
         for item, ent in ents:
             if ent is None:
                 lease = item.get("lease")
@@ -132,12 +155,17 @@ class EngineDriver:
                     fut.set_result(item)
         for loop, pairs in by_loop.items():
             loop.call_soon_threadsafe(done, pairs)
+        for hook in hooks:     # off the lock: the placer tops this engine up (which submits again)
+            hook()
 
     def _fail_all(self, exc: BaseException):
         with self._lock:
             pend, self._pending = self._pending, {}
+            hooks, self._on_resolved = self._on_resolved, {}
         for loop, fut in pend.values():
             loop.call_soon_threadsafe(lambda f=fut: (not f.done()) and f.set_exception(exc))
+        for hook in hooks.values():
+            hook()
 
     def _drain(self, step_error: Optional[BaseException] = None):
         while True:                    # a vocoder batch (or a failed step) can finish more than one poll's worth at once

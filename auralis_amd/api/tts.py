@@ -36,6 +36,9 @@ class TTS:
 
     # ------------------------------------------------------------------ model loading
     def from_pretrained(self, model_name_or_path: str, **kwargs) -> "TTS":
+        """kwargs go to the engine plugin's from_pretrained.  For XTTSv2Engine: `device=` (one engine, the default) or
+        `devices=[0, 1, ...]` (one engine per entry in this process, chunks placed by api/dispatch.py; both at once is a
+        ValueError); `max_concurrency` -- default: this facade's scheduler_max_concurrency -- is slots PER ENGINE."""
         cfg_path = os.path.join(model_name_or_path, "config.json")
         if not os.path.isfile(cfg_path):
             cfg_path = os.path.join(model_name_or_path, "core_xttsv2", "config.json")
@@ -139,8 +142,8 @@ class TTS:
         if self.tts_engine:
             if keep_engine:   # stop the plugin's driver thread, leave the native engine to its owner (with_engine callers)
                 drv = getattr(self.tts_engine, "driver", None)
-                if drv is not None:
-                    drv.shutdown()
+                for d in getattr(self.tts_engine, "drivers", None) or ([drv] if drv is not None else []):
+                    d.shutdown()
             else:
                 await self.tts_engine.shutdown()
 

@@ -13,11 +13,13 @@ import collections
 import hashlib
 import json
 import os
+import threading
 import time
-from typing import Any, AsyncGenerator, List, Optional, Tuple
+from typing import Any, AsyncGenerator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .dispatch import ChunkPlacer, EngineUnavailable
 from .driver import EngineDriver
 from .engine_base import BaseAsyncTTSEngine, ConditioningConfig, register_model
 from .output import TTSOutput
@@ -55,11 +57,29 @@ class ChunkHandle:
             fut.get_loop().call_soon_threadsafe(fut.cancel)
 
 
+class _Chunk:
+    """One chunk on its way through the placer (several engines): its future, what to submit, and where it is."""
+    __slots__ = ("future", "loop", "seq", "key", "g", "s", "engine", "sid")
+
+    def __init__(self, future, loop, seq, key, g, s):
+        self.future, self.loop, self.seq, self.key, self.g, self.s = future, loop, seq, key, g, s
+        self.engine = -1      # index of the engine it was placed on (-1: still in the placer's queue)
+        self.sid = None       # its sequence id there
+
+
 class XTTSv2Engine(BaseAsyncTTSEngine):
     model_type = "xtts"
 
     def __init__(self, native_engine: Any, tokenizer: XTTSTokenizer, max_concurrency: int = 10,
                  gpt_max_audio_tokens: int = 605, conditioning_weights: Optional[dict] = None):
+        """`native_engine`: one engine, or a sequence of them (one per GPU; the same GPU may carry more than one).  With a sequence
+        the plugin holds `natives`, one EngineDriver each in `drivers`, and a ChunkPlacer (api/dispatch.py) that decides where a
+        chunk runs; `native` / `driver` stay as names of the first.  `max_concurrency` is slots PER ENGINE."""
+        many = isinstance(native_engine, (list, tuple))
+        self.natives = list(native_engine) if many else [native_engine]
+        if not self.natives:
+            raise ValueError("XTTSv2Engine needs at least one native engine")
+        native_engine = self.natives[0]
         self.native = native_engine
         self.conditioning_weights = conditioning_weights   # xtts-v2.safetensors tensors of the once-per-speaker modules
         self._cond_cache = collections.OrderedDict()   # LRU, bounded (a serving process sees an open-ended set of voices)
@@ -68,6 +88,15 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
         self.max_concurrency = max_concurrency
         self.gpt_max_audio_tokens = gpt_max_audio_tokens
         self.driver = EngineDriver(native_engine)
+        self.drivers = [self.driver] + [EngineDriver(n) for n in self.natives[1:]]
+        # one engine: no placer, chunks go straight to its driver as they always did
+        self._placer: Optional[ChunkPlacer] = None
+        if len(self.natives) > 1:
+            self._placer_lock = threading.Lock()     # every call into the placer, from the event loop and from the driver threads
+            self._placer = ChunkPlacer([int(getattr(n, "max_seqs", max_concurrency)) for n in self.natives], self._place,
+                                       budget=lambda e: self.natives[e].load()["token_budget"],
+                                       running=lambda e: self.natives[e].load()["running"])
+            self._speakers_on = [dict() for _ in self.natives]   # engines without aur_has_conditioning (test doubles)
         self._speakers = {}
         self._seed_counter = 0
         # bench / test knob (aur_seq_desc.ignore_stop): every chunk runs to gpt_max_audio_tokens whatever it samples, so that
@@ -76,15 +105,28 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def from_pretrained(cls, pretrained_model_name_or_path: str, max_concurrency: int = 10, device: int = 0,
-                        vocoder: str = "fp16", gpt: str = "fp32", kv: str = "fp32", **kwargs) -> "XTTSv2Engine":
+    def from_pretrained(cls, pretrained_model_name_or_path: str, max_concurrency: int = 10, device: Optional[int] = None,
+                        vocoder: str = "fp16", gpt: str = "fp32", kv: str = "fp32", devices: Optional[Sequence[int]] = None,
+                        **kwargs) -> "XTTSv2Engine":
         """Load a checkpoint directory in the reference's on-disk format (checkpoint.py docstring).  kwargs the
         reference forwards to vLLM (tensor_parallel_size, pipeline_parallel_size, gpt_model, torch_dtype, device_map;
         XTTSv2.py:235-243) are accepted; tp/pp other than 1 are rejected (the path shards by utterance).
         `admit_min_batch` / `vocoder_min_batch` are the batcher's two grouping knobs, `max_speakers` the size of the engine's voice
         table (include/auralis_amd.h, aur_config).  gpt="fp16" keeps the four per-layer GPT linears as fp16 for the decode GEMMs
         (aur_config.gpt_fp16: the exact model on effective weights, weights.gpt_fp16_effective), kv="fp16" the K/V pool
-        (aur_config.kv_fp16); "fp32" (default) is the exact contract for both."""
+        (aur_config.kv_fp16); "fp32" (default) is the exact contract for both.
+
+        `device` (default 0): the GPU of the one engine.  `devices=[0, 1, ...]`: one engine per entry, all in this process, behind
+        a ChunkPlacer; the checkpoint is read and packed once and loaded into each.  A device may appear twice (two engines on one
+        GPU).  `max_concurrency` is slots PER ENGINE: devices=[0, 1, 2, 3] with max_concurrency=64 decodes up to 256 chunks at
+        once.  Passing both `device` and `devices` is a ValueError."""
+        if device is not None and devices is not None:
+            raise ValueError("pass device= (one engine) or devices= (one engine per entry), not both")
+        if devices is not None:
+            devices = [int(d) for d in devices]
+            if not devices:
+                raise ValueError("devices= needs at least one device index")
+        device = 0 if device is None else device
         from .._lib import NativeEngine
         from ..checkpoint import load_checkpoint, read_checkpoint_config
         from ..weights import pack_all
@@ -99,15 +141,24 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
         ck = read_checkpoint_config(pretrained_model_name_or_path, gpt_sd)
         # vocoder="fp16": HiFi-GAN convs on fp16-input / fp32-accumulate MFMA (waveform within 1e-5 RMS of the fp32
         # path, the reference's own GPU path autocasts to fp16); vocoder="fp32": exact-f32 MFMA parity mode
-        native = NativeEngine(n_layer=ck.n_layer, max_seqs=max(1, max_concurrency), device=device,
-                              vocoder_fp16=(vocoder == "fp16"), return_latents=False, gelu_erf=ck.gelu_erf,
-                              admit_min_batch=int(kwargs.get("admit_min_batch", 0)), vocoder_min_batch=int(kwargs.get("vocoder_min_batch", 0)),
-                              max_speakers=int(kwargs.get("max_speakers", 0)), urgent_rows=int(kwargs.get("urgent_rows", 0)),
-                              gpt_fp16=(gpt == "fp16"), kv_fp16=(kv == "fp16"))
-        native.load_weights(pack_all(gpt_sd, xtts_sd))
+        def make(dev):
+            return NativeEngine(n_layer=ck.n_layer, max_seqs=max(1, max_concurrency), device=dev,
+                                vocoder_fp16=(vocoder == "fp16"), return_latents=False, gelu_erf=ck.gelu_erf,
+                                admit_min_batch=int(kwargs.get("admit_min_batch", 0)), vocoder_min_batch=int(kwargs.get("vocoder_min_batch", 0)),
+                                max_speakers=int(kwargs.get("max_speakers", 0)), urgent_rows=int(kwargs.get("urgent_rows", 0)),
+                                gpt_fp16=(gpt == "fp16"), kv_fp16=(kv == "fp16"))
+        packed = pack_all(gpt_sd, xtts_sd)
+        packed_cond = None
         if any(k.startswith("conditioning_encoder.") for k in xtts_sd):
             from ..weights import pack_conditioning
-            native.load_weights(pack_conditioning(xtts_sd))
+            packed_cond = pack_conditioning(xtts_sd)
+        natives = []
+        for dev in ([device] if devices is None else devices):
+            native = make(dev)
+            natives.append(native)
+            native.load_weights(packed)
+            if packed_cond is not None:
+                native.load_weights(packed_cond)
         tok_file = None
         for cand in ("tokenizer.json", os.path.join("gpt", "tokenizer.json")):
             p = os.path.join(pretrained_model_name_or_path, cand)
@@ -121,7 +172,7 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
         vocab = xtts_sd["text_embedding.weight"].shape[0]
         cond_w = {k: v for k, v in xtts_sd.items()
                   if k.startswith(("conditioning_", "hifigan_decoder.speaker_encoder.", "mel_stats"))}
-        return cls(native, XTTSTokenizer(tok_file, vocab_size=vocab, synthetic=synthetic_tok), max_concurrency=max_concurrency,
+        return cls(natives[0] if devices is None else natives, XTTSTokenizer(tok_file, vocab_size=vocab, synthetic=synthetic_tok), max_concurrency=max_concurrency,
                    gpt_max_audio_tokens=ck.gpt_max_audio_tokens,
                    conditioning_weights=cond_w if any(k.startswith("conditioning_encoder.") for k in cond_w) else None)
 
@@ -141,7 +192,25 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
         """KV blocks per concurrent sequence (replaces the vLLM gpu_memory_utilization heuristic, XTTSv2.py:152-171)."""
         s = self.native.stats()
         per_seq_mb = 66 * 2 * 16 * 16 * 64 * 4 * self.native.n_layer / 2 ** 20
-        return {"kv_mb_per_sequence": per_seq_mb, "kv_blocks_total": s.get("kv_blocks_total", 0)}
+        out = {"kv_mb_per_sequence": per_seq_mb, "kv_blocks_total": s.get("kv_blocks_total", 0)}
+        if self._placer is not None:   # several engines: the values above are the first one's, every engine's are listed
+            out["engines"] = [{"kv_mb_per_sequence": 66 * 2 * 16 * 16 * 64 * 4 * n.n_layer / 2 ** 20,
+                               "kv_blocks_total": n.stats().get("kv_blocks_total", 0), "max_seqs": getattr(n, "max_seqs", None),
+                               "device": getattr(n, "device", None)} for n in self.natives]
+        return out
+
+    def load(self) -> List[dict]:
+        """aur_get_load of every engine, in `natives` order: {waiting, running, vocoding, free_slots, token_budget} (host only; safe
+        while the engines step)."""
+        return [n.load() for n in self.natives]
+
+    def _least_loaded_native(self):
+        """Where once-per-voice work (aur_compute_conditioning) runs: with several engines, the one with the least ahead of it."""
+        if self._placer is None:
+            return self.native
+        loads = self.load()
+        e = min(range(len(loads)), key=lambda i: (loads[i]["waiting"] + loads[i]["running"] + loads[i]["vocoding"], loads[i]["token_budget"], i))
+        return self.natives[e]
 
     # ------------------------------------------------------------------ conditioning
     async def get_audio_conditioning(self, audio_reference, max_ref_length=30, gpt_cond_len=6, gpt_cond_chunk_len=6,
@@ -182,7 +251,7 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
             if key in self._cond_cache:
                 self._cond_cache.move_to_end(key)
             else:
-                hip = getattr(self.native, "compute_conditioning", None)
+                hip = getattr(self._least_loaded_native(), "compute_conditioning", None)
                 if hip is None:
                     raise RuntimeError("the engine has no compute_conditioning entry point: speaker conditioning from reference "
                                        "audio runs in HIP (aur_compute_conditioning); there is no PyTorch fallback in the product")
@@ -227,7 +296,8 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
                 request.speaker_files, request.max_ref_length, request.gpt_cond_len, request.gpt_cond_chunk_len)
         g_np = np.asarray(gpt_cond_latent, dtype=np.float32)
         s_np = np.asarray(speaker_embeddings, dtype=np.float32)
-        key = self._register_speaker(g_np, s_np)
+        # (several engines: a voice is registered on an engine when a chunk is placed there, _place)
+        key = self._register_speaker(g_np, s_np) if self._placer is None else _content_key(g_np, s_np)
         chunks = self.tokenizer.batch_encode_with_split(request.text, request.language)
         loop = asyncio.get_running_loop()
         handles, ids = [], []
@@ -239,20 +309,92 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
                         ^ self._seed_counter) & 0xFFFFFFFF
             else:
                 seed = (request.seed + idx) & 0xFFFFFFFF
-            fut = self.driver.submit(loop, reregister=lambda: self.native.set_conditioning(key, g_np, s_np),
-                                     text_ids=text_ids, speaker_key=key, temperature=request.temperature,
-                                     top_p=request.top_p, top_k=request.top_k,
-                                     repetition_penalty=request.repetition_penalty,
-                                     max_tokens=self.gpt_max_audio_tokens, seed=seed,
-                                     **({"ignore_stop": True} if self.fixed_length else {}),
-                                     # a latency-critical request: its first chunk is the one somebody waits for
-                                     **({"priority": int(request.priority)} if idx == 0 and getattr(request, "priority", 0) > 0 else {}),
-                                     # the speaking rate belongs to the whole request: every chunk carries it
-                                     **({"speed": float(request.speed)} if getattr(request, "speed", 1.0) != 1.0 else {}))
+            seq = dict(text_ids=text_ids, speaker_key=key, temperature=request.temperature,
+                       top_p=request.top_p, top_k=request.top_k,
+                       repetition_penalty=request.repetition_penalty,
+                       max_tokens=self.gpt_max_audio_tokens, seed=seed,
+                       **({"ignore_stop": True} if self.fixed_length else {}),
+                       # a latency-critical request: its first chunk is the one somebody waits for
+                       **({"priority": int(request.priority)} if idx == 0 and getattr(request, "priority", 0) > 0 else {}),
+                       # the speaking rate belongs to the whole request: every chunk carries it
+                       **({"speed": float(request.speed)} if getattr(request, "speed", 1.0) != 1.0 else {}))
+            if self._placer is None:
+                fut = self.driver.submit(loop, reregister=lambda: self.native.set_conditioning(key, g_np, s_np), **seq)
+            else:
+                fut = self._submit_placed(loop, seq, key, g_np, s_np)
             rid = f"{request.request_id}_{idx}"
             handles.append(ChunkHandle(fut, rid, len(text_ids)))
             ids.append(rid)
         return handles, ids, speaker_embeddings, gpt_cond_latent
+
+    # ------------------------------------------------------------------ several engines: placement
+    def _submit_placed(self, loop, seq: dict, key: int, g_np: np.ndarray, s_np: np.ndarray) -> "asyncio.Future":
+        """Event loop: the chunk's future exists from now on, the chunk itself goes to the placer -- onto an engine at once if one has
+        room, into the placer's queue otherwise."""
+        chunk = _Chunk(loop.create_future(), loop, seq, key, g_np, s_np)
+        # a consumer that walks away cancels the future: the chunk leaves the placer's queue, or its engine is told (aur_cancel)
+        chunk.future.add_done_callback(lambda f, c=chunk: self._chunk_done(f, c))
+        with self._placer_lock:
+            self._placer.submit(chunk, int(seq.get("priority", 0)))
+            self._fail_orphans()
+        return chunk.future
+
+    def _register_on(self, e: int, chunk: _Chunk):
+        """The has_conditioning / set_conditioning handshake of _register_speaker, on engine e."""
+        native = self.natives[e]
+        has = getattr(native, "has_conditioning", None)
+        if has is not None:
+            if not has(chunk.key):
+                native.set_conditioning(chunk.key, chunk.g, chunk.s)
+        elif chunk.key not in self._speakers_on[e]:
+            native.set_conditioning(chunk.key, chunk.g, chunk.s)
+            self._speakers_on[e][chunk.key] = True
+
+    def _place(self, e: int, chunk: _Chunk):
+        """ChunkPlacer's callback (placer lock held; event loop or a driver thread).  Never waits for an event loop.  It can wait for
+        an ENGINE, though: the first placement of a voice on engine e (or its re-registration after an eviction) is
+        aur_set_conditioning, which waits for e's running step, and the placer lock is held meanwhile -- the other drivers' hooks and
+        the event loop's submissions queue up behind it for that long.  No deadlock (a step never takes the placer lock); the cost
+        is unmeasured."""
+        drv = self.drivers[e]
+        if drv._error is not None or drv._stop:
+            raise EngineUnavailable(f"engine {e}: driver stopped")
+        native = self.natives[e]
+        try:
+            self._register_on(e, chunk)
+            chunk.sid = drv.submit_for(chunk.future, chunk.loop, on_resolved=lambda: self._resolved(e),
+                                       reregister=lambda: native.set_conditioning(chunk.key, chunk.g, chunk.s), **chunk.seq)
+            chunk.engine = e
+            return True
+        except Exception as exc:   # noqa: BLE001 - this chunk's own failure (a bad id, a full voice table): its future gets it
+            if drv._error is not None:
+                raise EngineUnavailable(f"engine {e}: driver stopped") from exc
+            chunk.loop.call_soon_threadsafe(lambda f=chunk.future, x=exc: (not f.done()) and f.set_exception(x))
+            return False
+
+    def _resolved(self, e: int):
+        """Driver thread of engine e: one of its sequences has resolved; the placer tops the engine up (or, when the driver has
+        stopped, takes the engine out and routes what is queued to the others)."""
+        with self._placer_lock:
+            gone = self._placer.engine_dead(e) if self.drivers[e]._error is not None and self._placer.alive[e] else []
+            self._placer.resolved(e)
+            self._fail_orphans(gone)
+
+    def _fail_orphans(self, gone=()):
+        """(placer lock held) chunks still queued when the last engine went: their futures fail, as a stopped driver's do."""
+        for chunk in list(gone) + self._placer.orphans():
+            exc = RuntimeError("engine driver stopped: no engine left to place the chunk on")
+            chunk.loop.call_soon_threadsafe(lambda f=chunk.future, x=exc: (not f.done()) and f.set_exception(x))
+
+    def _chunk_done(self, fut: "asyncio.Future", chunk: _Chunk):
+        if not fut.cancelled():
+            return
+        with self._placer_lock:
+            if self._placer.cancel(chunk):      # still queued: no engine ever sees it
+                return
+            e, sid = chunk.engine, chunk.sid
+        if e >= 0 and sid is not None:
+            self.drivers[e].cancel_seq(sid)
 
     # ------------------------------------------------------------------ phase 2
     async def process_tokens_to_speech(self, generator: ChunkHandle, speaker_embeddings=None, multimodal_data=None,
@@ -266,10 +408,21 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
                         token_length=int(len(item["tokens"])))
 
     async def shutdown(self):
-        self.driver.shutdown()
-        close = getattr(self.native, "close", None)
-        if close:
-            close()
+        if self._placer is not None:
+            with self._placer_lock:   # nothing is placed from here on; what still waits in the placer's queue fails now
+                gone = []
+                for e in range(len(self.natives)):
+                    gone += self._placer.engine_dead(e)
+                self._fail_orphans(gone)
+        for drv in self.drivers:      # every driver first: no thread steps an engine while another one is closed
+            drv.shutdown()
+        if self._placer is not None:  # what was on an engine gets the same answer as what was still queued
+            for drv in self.drivers:
+                drv._fail_all(RuntimeError("engine shut down"))
+        for native in self.natives:
+            close = getattr(native, "close", None)
+            if close:
+                close()
 
 
 register_model("xtts", XTTSv2Engine)

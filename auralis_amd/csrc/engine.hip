@@ -9,6 +9,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -104,6 +105,7 @@ struct Seq {
     int n_prompt = 0;
     std::vector<int> blocks;
     std::vector<int32_t> tokens;
+    std::atomic<int32_t> n_gen{0};    // tokens.size(), readable under mu_ alone while the driver thread appends (aur_get_load)
     const float* wav = nullptr;       // into `result_block`
     int n_samples = 0;
     const float* latents = nullptr;   // into `result_block` (aur_config.return_latents)
@@ -912,6 +914,24 @@ public:
         s.sequences_tracked = (int64_t)seqs_.size();
         return s;
     }
+    // aur_get_load.  Host only: the queue lock and nothing else -- no HIP call, no wait for a running step.  Everything read here is
+    // written under mu_ (Seq::state, slot_owner_, seqs_) or atomic (Seq::n_gen); the vocoder queue and the token vectors, which the
+    // driver thread changes without the lock, are not looked at.
+    aur_load load_now() {
+        std::lock_guard<std::mutex> lk(mu_);
+        aur_load l{};
+        for (auto& kv : seqs_) {
+            const Seq& s = *kv.second;
+            if (s.state == SeqState::WAITING) l.waiting++;
+            else if (s.state == SeqState::RUNNING) l.running++;
+            else if (s.state == SeqState::TOKENS_DONE) l.vocoding++;
+            if (s.state == SeqState::WAITING || s.state == SeqState::RUNNING)
+                l.token_budget += std::max(0, s.params.max_tokens - s.n_gen.load(std::memory_order_relaxed));
+        }
+        for (const Seq* s : slot_owner_)
+            if (!s) l.free_slots++;
+        return l;
+    }
     void reset_stats() {
         std::lock_guard<std::mutex> lk(mu_);
         stats_ = aur_stats{};
@@ -1383,6 +1403,7 @@ private:
         for (int j = 0; j < Ms; ++j) {
             Seq* s = slot_owner_[sample_slot[j]];
             s->tokens.push_back(pin[j] & ~kTokFinishedBit);
+            s->n_gen.fetch_add(1, std::memory_order_relaxed);
             stats_.tokens_generated++;
             if (pin[j] & kTokFinishedBit) just_finished_.push_back(s);
         }
@@ -1603,6 +1624,7 @@ private:
             Seq* s = slot_owner_[f.slots[j]];
             AUR_REQUIRE(s && s->state == SeqState::RUNNING, "decode read-back for a slot without a running sequence");
             s->tokens.push_back(tok);
+            s->n_gen.fetch_add(1, std::memory_order_relaxed);
             stats_.tokens_generated++;
             ++rows;
             if (raw & kTokFinishedBit) just_finished_.push_back(s);
@@ -2098,6 +2120,21 @@ struct aur_engine {
 
 aur::DbgCtx aur::dbg_ctx(const aur_engine* e) { return e->impl.dbg_ctx(); }
 
+// Device binding.  HIP's current device belongs to the calling THREAD, and one process may hold engines on several devices driven from
+// several threads (a driver thread per engine, the event loop, whichever thread drops a result lease).  Every entry point that can reach
+// a HIP call therefore goes through bound(): it binds the calling thread to the engine's device before anything else runs.  The others
+// are host-only -- they take mu_ and make no HIP call -- and bind nothing: aur_has_conditioning, aur_comm_info, aur_submit,
+// aur_poll_finished, aur_release, aur_cancel, aur_get_stats, aur_reset_stats, aur_get_load, aur_set_profile.  aur_engine_create and
+// aur_engine_destroy bind in the constructor / destructor, aur_step at the top of step_locked (inside its failure handling); the
+// aur_dbg_* harness binds in its own use() (dbg_harness.hip).
+template <class F>
+static int bound(aur_engine* e, F&& f) {
+    return guarded([&] {
+        e->impl.use();
+        f();
+    });
+}
+
 extern "C" {
 
 const char* aur_last_error(void) { return aur::g_last_error.c_str(); }
@@ -2122,19 +2159,19 @@ int aur_engine_destroy(aur_engine* e) {
 int aur_load_weights(aur_engine* e, const aur_tensor_desc* t, size_t n) {
     CHECK_PTR(e);
     CHECK_PTR(t);
-    return guarded([&] { e->impl.load(t, n); });
+    return bound(e, [&] { e->impl.load(t, n); });
 }
 int aur_set_conditioning(aur_engine* e, uint64_t key, const float* gpt_cond, const float* spk) {
     CHECK_PTR(e);
     CHECK_PTR(gpt_cond);
     CHECK_PTR(spk);
-    return guarded([&] { e->impl.set_conditioning(key, gpt_cond, spk, false); });
+    return bound(e, [&] { e->impl.set_conditioning(key, gpt_cond, spk, false); });
 }
 int aur_set_conditioning_device(aur_engine* e, uint64_t key, const float* d_gpt_cond, const float* d_spk) {
     CHECK_PTR(e);
     CHECK_PTR(d_gpt_cond);
     CHECK_PTR(d_spk);
-    return guarded([&] { e->impl.set_conditioning(key, d_gpt_cond, d_spk, true); });
+    return bound(e, [&] { e->impl.set_conditioning(key, d_gpt_cond, d_spk, true); });
 }
 int aur_has_conditioning(aur_engine* e, uint64_t key, int32_t* out) {
     CHECK_PTR(e);
@@ -2148,11 +2185,11 @@ int aur_comm_unique_id(uint8_t* out128) {
 int aur_comm_init(aur_engine* e, const uint8_t* id128, int32_t rank, int32_t world) {
     CHECK_PTR(e);
     CHECK_PTR(id128);
-    return guarded([&] { e->impl.comm_init(id128, rank, world); });
+    return bound(e, [&] { e->impl.comm_init(id128, rank, world); });
 }
 int aur_broadcast_conditioning(aur_engine* e, uint64_t key, int32_t root) {
     CHECK_PTR(e);
-    return guarded([&] { e->impl.broadcast_conditioning(key, root); });
+    return bound(e, [&] { e->impl.broadcast_conditioning(key, root); });
 }
 int aur_comm_info(aur_engine* e, int32_t* n_ranks, int32_t* rank) {
     CHECK_PTR(e);
@@ -2163,7 +2200,7 @@ int aur_comm_info(aur_engine* e, int32_t* n_ranks, int32_t* rank) {
 int aur_conditioning_checksum(aur_engine* e, uint64_t key, uint64_t* out) {
     CHECK_PTR(e);
     CHECK_PTR(out);
-    return guarded([&] { *out = e->impl.conditioning_checksum(key); });
+    return bound(e, [&] { *out = e->impl.conditioning_checksum(key); });
 }
 int aur_compute_conditioning(aur_engine* e, const float* const* pcm, const int32_t* n_samples, int32_t n_refs, const aur_cond_params* p,
                              float* out_gpt_cond, float* out_spk_emb) {
@@ -2173,7 +2210,7 @@ int aur_compute_conditioning(aur_engine* e, const float* const* pcm, const int32
     CHECK_PTR(p);
     CHECK_PTR(out_gpt_cond);
     CHECK_PTR(out_spk_emb);
-    return guarded([&] { e->impl.compute_conditioning(pcm, n_samples, n_refs, *p, out_gpt_cond, out_spk_emb); });
+    return bound(e, [&] { e->impl.compute_conditioning(pcm, n_samples, n_refs, *p, out_gpt_cond, out_spk_emb); });
 }
 int aur_submit(aur_engine* e, const aur_seq_desc* seq, uint64_t* seq_id) {
     CHECK_PTR(e);
@@ -2183,6 +2220,7 @@ int aur_submit(aur_engine* e, const aur_seq_desc* seq, uint64_t* seq_id) {
 }
 int aur_step(aur_engine* e, int32_t* n_live, int32_t* n_finished_total) {
     CHECK_PTR(e);
+    // (binds first thing inside, in step_locked, where a failure fails what was in flight)
     return guarded([&] { e->impl.step(n_live, n_finished_total); });
 }
 int aur_poll_finished(aur_engine* e, aur_result* out, size_t cap, size_t* n) {
@@ -2209,16 +2247,21 @@ int aur_vocode_speed(aur_engine* e, const float* latents, const int32_t* n_lat, 
     CHECK_PTR(latents);
     CHECK_PTR(n_lat);
     CHECK_PTR(wav_out);
-    return guarded([&] { e->impl.vocode_host(latents, n_lat, speed, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out); });
+    return bound(e, [&] { e->impl.vocode_host(latents, n_lat, speed, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out); });
 }
 int aur_sync(aur_engine* e) {
     CHECK_PTR(e);
-    return guarded([&] { e->impl.sync(); });
+    return bound(e, [&] { e->impl.sync(); });
 }
 int aur_get_stats(aur_engine* e, aur_stats* out) {
     CHECK_PTR(e);
     CHECK_PTR(out);
     return guarded([&] { *out = e->impl.stats(); });
+}
+int aur_get_load(aur_engine* e, aur_load* out) {
+    CHECK_PTR(e);
+    CHECK_PTR(out);
+    return guarded([&] { *out = e->impl.load_now(); });
 }
 int aur_reset_stats(aur_engine* e) {
     CHECK_PTR(e);
@@ -2232,14 +2275,14 @@ int aur_dbg_prefill(aur_engine* e, const int32_t* text_ids, int32_t n_text, uint
                     float* lnf_rows_out, float* logits_out) {
     CHECK_PTR(e);
     CHECK_PTR(text_ids);
-    return guarded([&] { e->impl.dbg_prefill(text_ids, n_text, speaker_key, repetition_penalty, lnf_rows_out, logits_out); });
+    return bound(e, [&] { e->impl.dbg_prefill(text_ids, n_text, speaker_key, repetition_penalty, lnf_rows_out, logits_out); });
 }
 int aur_dbg_sample(aur_engine* e, const float* logits, int32_t B, float temperature, float top_p, int32_t top_k,
                    float repetition_penalty, const uint8_t* seen, uint32_t seed, int32_t step, int32_t* tokens_out) {
     CHECK_PTR(e);
     CHECK_PTR(logits);
     CHECK_PTR(tokens_out);
-    return guarded([&] { e->impl.dbg_sample(logits, B, temperature, top_p, top_k, repetition_penalty, seen, seed, step, tokens_out); });
+    return bound(e, [&] { e->impl.dbg_sample(logits, B, temperature, top_p, top_k, repetition_penalty, seen, seed, step, tokens_out); });
 }
 
 }  // extern "C"

@@ -276,6 +276,17 @@ def create_app(tts: Optional[TTS], speed_mode: str = "stretch") -> FastAPI:
     return app
 
 
+def _device_list(text: str):
+    """--devices 0,1,2,3 -> [0, 1, 2, 3] (a device may appear twice: two engines on one GPU)"""
+    try:
+        out = [int(t) for t in text.split(",") if t.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--devices: expected comma-separated integers, got {text!r}")
+    if not out or min(out) < 0:
+        raise argparse.ArgumentTypeError(f"--devices: expected at least one non-negative device index, got {text!r}")
+    return out
+
+
 def main():
     import uvicorn
     p = argparse.ArgumentParser(description="auralis_amd TTS FastAPI server")
@@ -290,8 +301,12 @@ def main():
     p.add_argument("--speed-mode", choices=("stretch", "latent"), default="stretch",
                    help="the request's `speed`: stretch = phase vocoder over the finished waveform (the reference's behaviour); "
                         "latent = the engine stretches the GPT latents ahead of the vocoder (TTSRequest.speed, clamped to [0.5, 2.0])")
+    p.add_argument("--devices", type=_device_list, default=None, metavar="0,1,2,3",
+                   help="comma-separated GPU indices: one engine per entry in this process, chunks placed on the least loaded one "
+                        "(--max_concurrency is then slots PER ENGINE); default: one engine on device 0")
     a = p.parse_args()
-    tts = TTS(scheduler_max_concurrency=a.max_concurrency).from_pretrained(a.model, gpt=a.gpt, kv=a.kv)
+    tts = TTS(scheduler_max_concurrency=a.max_concurrency).from_pretrained(a.model, gpt=a.gpt, kv=a.kv,
+                                                                           **({"devices": a.devices} if a.devices is not None else {}))
     uvicorn.run(create_app(tts, speed_mode=a.speed_mode), host=a.host, port=a.port)
 
 

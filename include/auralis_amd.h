@@ -195,6 +195,16 @@ typedef struct aur_stats {
     int64_t sequences_tracked;     /* sequences the engine still holds (waiting, running, vocoding, or finished and not yet released) */
 } aur_stats;
 
+/* What an engine has on its hands right now: what a dispatcher over several engines (one per GPU) places work by. */
+typedef struct aur_load {
+    int32_t waiting;               /* submitted, no slot yet */
+    int32_t running;               /* decoding in a slot */
+    int32_t vocoding;              /* tokens done, waiting for or inside a vocoder batch */
+    int32_t free_slots;            /* of aur_config.max_seqs */
+    int64_t token_budget;          /* sum over waiting and running sequences of max_tokens - tokens generated so far: an upper bound on
+                                      the decode work still ahead of the engine */
+} aur_load;
+
 const char* aur_last_error(void);
 int aur_version(void);
 
@@ -280,6 +290,9 @@ int aur_vocode_speed(aur_engine* e, const float* latents, const int32_t* n_lat, 
 int aur_sync(aur_engine* e);
 int aur_get_stats(aur_engine* e, aur_stats* out);
 int aur_reset_stats(aur_engine* e);
+/* Host only: takes the engine's submission lock and nothing else -- no HIP call, no synchronisation, does not wait for a running
+ * aur_step.  Safe from any thread at any time.  New surface; the reference has no counterpart. */
+int aur_get_load(aur_engine* e, aur_load* out);
 /* Profile mode at run time (new surface; the reference has no counterpart): every > 0 -- HIP events around every vocoder conv
  * launch, and after every `every`-th decode step the per-kind replay batches described at aur_stats.gemm_kind_*; 0 = off (the
  * configuration the parity tests run).  Results of the sequences are the same either way. */
