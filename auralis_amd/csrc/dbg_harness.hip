@@ -1,13 +1,15 @@
 // Kernel test harness: the aur_dbg_* entry points of include/auralis_amd.h that run ONE kernel on host arrays (tests/test_gpu_kernels.py,
 // test_gpu_prefill_kernels.py, test_gpu_vocoder_kernels.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
-// the K-split scratch (DbgCtx) and nothing else; aur_dbg_prefill and aur_dbg_sample drive real engine state and live in engine.hip.
+// the K-split scratch (DbgCtx) and nothing else, and the host rules of a launch from where the engine takes them: gpt_host.h (the decode
+// GEMMs' operands) and voc_net.h (the storage of a vocoder conv's tensors); aur_dbg_prefill and aur_dbg_sample drive real engine state
+// and live in engine.hip.
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
 
 #include "abi_internal.h"
 #include "gpt_host.h"
-#include "vocoder_kernels.h"
+#include "voc_net.h"
 
 namespace aur {
 
@@ -102,40 +104,6 @@ static long long download_kv_pool(const DevBuf& dpool, int n_seq, int ctx_max, b
     return stray;
 }
 
-static void dbg_conv1d(const aur_engine* e, const float* x, const void* wp, const float* bias, const float* res, float* out, const int* lens,
-                       int B, int Cin, int Mtot, int Cout, int L, int KS, int DIL, int padl, float slope, int ups_s, int ups_p, bool f16) {
-    const DbgCtx c = use(e);
-    const int Lout = L * std::max(1, ups_s);
-    const size_t n_out = (size_t)B * Cout * Lout * 4;
-    DevBuf dx, dw, db, dr, dout, dl;
-    dx.upload(x, (size_t)B * Cin * L * 4);
-    dw.upload(wp, (size_t)Mtot * Cin * KS * (f16 ? 2 : 4));
-    dl.upload(lens, (size_t)B * 4);
-    dout.zeros(n_out, c.st);
-    if (bias) db.upload(bias, (size_t)Cout * 4);
-    if (res) dr.upload(res, n_out);
-    ConvArgs a{};
-    a.x = dx.as<float>();
-    a.wp = dw.as<float>();
-    a.wp16 = dw.p;
-    a.bias = db.as<float>();
-    a.res = dr.as<float>();
-    a.out = dout.as<float>();
-    a.base_len = dl.as<int>();
-    a.len_mul = 1;
-    a.Cin = Cin; a.Mtot = Mtot; a.Cout = Cout;
-    a.x_stride = L; a.o_stride = Lout;
-    a.x_bstride = (long)Cin * L; a.o_bstride = (long)Cout * Lout;
-    a.padl = padl; a.slope = slope; a.ups_s = ups_s; a.ups_p = ups_p;
-    a.max_len = *std::max_element(lens, lens + B);
-    a.B = B;
-    if (f16)
-        launch_conv1d_f16(a, KS, DIL, c.st);
-    else
-        launch_conv1d(a, KS, DIL, c.st);
-    download(out, dout, n_out, c.st);
-}
-
 // ---- the vocoder's kernels on host arrays [B][C][L] (aur_dbg_conv1d_args, _resblock_round_f16, _interp2, _conv_post) ----
 constexpr size_t kGuardBytes = 4096;
 
@@ -198,6 +166,79 @@ static void check_lens(const int* lens, int B, int L, const char* what) {
     AUR_REQUIRE(B >= 1 && L >= 1, what);
     for (int b = 0; b < B; ++b) AUR_REQUIRE(lens[b] >= 1 && lens[b] <= L, what);
     AUR_REQUIRE(*std::max_element(lens, lens + B) == L, what);   // the row stride is the longest utterance, as in the engine
+}
+
+// aur_dbg_conv1d_args' variant as the engine's storage layout: 0 the fp32 vocoder, 1 / 2 interleaved halves, register / LDS-DMA staged
+static VocLayout variant_layout(int variant) { return {variant != 0, variant != 0, variant == 2}; }
+
+// One ConvArgs launch on host arrays [B][C][L], every tensor stored as the engine stores it under `lay` in the role the arguments
+// name (conv_storage, voc_net.h): ups_s > 0 a transposed conv, a residual the second conv of a ResBlock round, anything else the
+// first.  mrf and out go between guards of guard_value; returns the guard words that changed.
+static long long run_conv(const DbgCtx& c, VocLayout lay, const float* x, const void* w, const float* bias, const float* cond, const int* cond_row,
+                          int cond_rows, int cond_stride, const float* res, float* mrf, float* out, const int* lens, int B, int Cin, int Mtot,
+                          int Cout, int L, int KS, int DIL, int padl, float slope, int ups_s, int ups_p, int mrf_mode, float out_slope,
+                          float guard_value) {
+    const long Lout = (long)L * std::max(1, ups_s);
+    DevBuf dx, dw, db, dc, dcr, dr, dl, dz;
+    GuardedBuf gm, go;
+    if (lay.halves) {
+        AUR_REQUIRE(Cin % 16 == 0, "dbg_conv1d_args: interleaved halves need whole 16-channel chunks");
+        dx.upload(to_halves(x, B, Cin, L));
+        if (res) {
+            AUR_REQUIRE(Cout % 16 == 0, "dbg_conv1d_args: interleaved halves need whole 16-channel chunks");
+            dr.upload(to_halves(res, B, Cout, Lout));
+        }
+    } else {
+        dx.upload(x, (size_t)B * Cin * L * 4);
+        if (res) dr.upload(res, (size_t)B * Cout * Lout * 4);
+    }
+    dw.upload(w, (size_t)Mtot * Cin * KS * (lay.f16 ? 2 : 4));
+    dl.upload(lens, (size_t)B * 4);
+    if (bias) db.upload(bias, (size_t)Cout * 4);
+    if (cond) {
+        dc.upload(cond, (size_t)cond_rows * cond_stride * 4);
+        dcr.upload(cond_row, (size_t)B * 4);
+    }
+    if (lay.dma) dz.zeros(256, c.st);
+    ConvArgs a{};
+    a.x = dx.as<float>();
+    a.wp = dw.as<float>();
+    a.wp16 = lay.f16 ? dw.p : nullptr;
+    a.bias = db.as<float>();
+    a.cond = dc.as<float>(); a.cond_row = dcr.as<int>(); a.cond_stride = cond_stride;
+    a.res = dr.as<float>();
+    a.base_len = dl.as<int>();
+    a.len_mul = 1;
+    a.Cin = Cin; a.Mtot = Mtot; a.Cout = Cout;
+    a.x_stride = L; a.o_stride = Lout;
+    a.x_bstride = (long)Cin * L; a.o_bstride = (long)Cout * Lout;
+    a.padl = padl; a.slope = slope; a.ups_s = ups_s; a.ups_p = ups_p;
+    a.max_len = *std::max_element(lens, lens + B);
+    a.B = B;
+    conv_storage(a, lay, ups_s > 0 ? VocRole::Ups : res ? VocRole::C2 : VocRole::C1, mrf_mode, out_slope, dz.p);
+    if (mrf_mode != 0) {
+        gm.upload(mrf, B, Cout, Lout, a.mrf_f16 != 0, guard_value);
+        a.mrf = reinterpret_cast<float*>(gm.data());
+    }
+    if (mrf_mode == 0 || mrf_mode == 3) {
+        go.upload(out, B, Cout, Lout, a.out_act_f16 != 0, guard_value);
+        a.out = reinterpret_cast<float*>(go.data());
+    }
+    if (lay.f16)
+        launch_conv1d_f16(a, KS, DIL, c.st);
+    else
+        launch_conv1d(a, KS, DIL, c.st);
+    long long bad = 0;
+    if (mrf_mode != 0) bad += gm.download(mrf, c.st);
+    if (mrf_mode == 0 || mrf_mode == 3) bad += go.download(out, c.st);
+    return bad;
+}
+// aur_dbg_conv1d / _f16: the same launch on fp32 tensors (f16: fp16 weights and MFMA) without conditioning or MRF, into a zeroed output
+static void run_conv_plain(const aur_engine* e, bool f16, const float* x, const void* w, const float* bias, const float* res, float* out,
+                           const int* lens, int B, int Cin, int Mtot, int Cout, int L, int KS, int DIL, int padl, float slope, int ups_s, int ups_p) {
+    std::fill(out, out + (size_t)B * Cout * L * std::max(1, ups_s), 0.f);
+    run_conv(use(e), {f16, false, false}, x, w, bias, nullptr, nullptr, 0, 0, res, nullptr, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope,
+             ups_s, ups_p, 0, 0.f, 0.f);
 }
 
 }  // namespace aur
@@ -564,14 +605,17 @@ int aur_dbg_conv1d(aur_engine* e, const float* x, const float* wp, const float* 
                    const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout, int32_t L, int32_t KS,
                    int32_t DIL, int32_t padl, float slope, int32_t ups_s, int32_t ups_p) {
     CHECK_PTR(e);
-    return guarded([&] { dbg_conv1d(e, x, wp, bias, res, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope, ups_s, ups_p, false); });
+    return guarded([&] { run_conv_plain(e, false, x, wp, bias, res, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope, ups_s, ups_p); });
 }
 int aur_dbg_conv1d_f16(aur_engine* e, const float* x, const void* wp16, const float* bias, const float* res, float* out,
                        const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout, int32_t L, int32_t KS,
                        int32_t DIL, int32_t padl, float slope, int32_t ups_s, int32_t ups_p) {
     CHECK_PTR(e);
-    return guarded([&] { dbg_conv1d(e, x, wp16, bias, res, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope, ups_s, ups_p, true); });
+    return guarded([&] { run_conv_plain(e, true, x, wp16, bias, res, out, lens, B, Cin, Mtot, Cout, L, KS, DIL, padl, slope, ups_s, ups_p); });
 }
+// One ConvArgs launch as the engine would fill it (run_conv).  The storage flags come from conv_storage, so two arguments only carry what
+// the engine's rule leaves open: out_slope is used where the output is stored as activated halves, and res_unact is not read at all (a
+// halves residual is un-activated with the engine's 1 / 0.1).
 int aur_dbg_conv1d_args(aur_engine* e, int32_t variant, const float* x, const void* w, const float* bias, const float* cond,
                         const int32_t* cond_row, int32_t cond_rows, int32_t cond_stride, const float* res, float* mrf, float* out,
                         const int32_t* lens, int32_t B, int32_t Cin, int32_t Mtot, int32_t Cout, int32_t L, int32_t KS, int32_t DIL,
@@ -598,73 +642,8 @@ int aur_dbg_conv1d_args(aur_engine* e, int32_t variant, const float* x, const vo
         const bool half = variant != 0;
         // on halves KS == 2 is the transposed convs (out_act_f16 alone): a plain k = 2 conv would read a halves residual as floats
         AUR_REQUIRE(!half || KS != 2 || ups_s > 0, "dbg_conv1d_args: KS == 2 on interleaved halves is a transposed conv (ups_s > 0)");
-        const long Lout = (long)L * std::max(1, ups_s);
-        DevBuf dx, dw, db, dc, dcr, dr, dl, dz;
-        GuardedBuf gm, go;
-        if (half) {
-            AUR_REQUIRE(Cin % 16 == 0, "dbg_conv1d_args: interleaved halves need whole 16-channel chunks");
-            dx.upload(to_halves(x, B, Cin, L));
-            if (res) {
-                AUR_REQUIRE(Cout % 16 == 0, "dbg_conv1d_args: interleaved halves need whole 16-channel chunks");
-                dr.upload(to_halves(res, B, Cout, Lout));
-            }
-        } else {
-            dx.upload(x, (size_t)B * Cin * L * 4);
-            if (res) dr.upload(res, (size_t)B * Cout * Lout * 4);
-        }
-        dw.upload(w, (size_t)Mtot * Cin * KS * (half ? 2 : 4));
-        dl.upload(lens, (size_t)B * 4);
-        if (bias) db.upload(bias, (size_t)Cout * 4);
-        if (cond) {
-            dc.upload(cond, (size_t)cond_rows * cond_stride * 4);
-            dcr.upload(cond_row, (size_t)B * 4);
-        }
-        ConvArgs a{};
-        a.x = dx.as<float>();
-        a.wp = dw.as<float>();
-        a.wp16 = half ? dw.p : nullptr;
-        a.bias = db.as<float>();
-        a.cond = dc.as<float>(); a.cond_row = dcr.as<int>(); a.cond_stride = cond_stride;
-        a.res = dr.as<float>();
-        a.base_len = dl.as<int>();
-        a.len_mul = 1;
-        a.Cin = Cin; a.Mtot = Mtot; a.Cout = Cout;
-        a.x_stride = L; a.o_stride = Lout;
-        a.x_bstride = (long)Cin * L; a.o_bstride = (long)Cout * Lout;
-        a.padl = padl; a.slope = slope; a.ups_s = ups_s; a.ups_p = ups_p;
-        a.mrf_mode = mrf_mode; a.out_slope = out_slope; a.res_unact = res_unact;
-        a.max_len = L;
-        a.B = B;
-        if (half) {   // the tensor flags as run_vocoder sets them in fp16 mode
-            a.x_f16 = 1;
-            if (KS == 2) {
-                a.out_act_f16 = 1;
-            } else {
-                a.res_f16 = res ? 1 : 0;
-                a.mrf_f16 = mrf_mode != 0 ? 1 : 0;
-                a.out_act_f16 = (mrf_mode == 0 || mrf_mode == 3) ? 1 : 0;
-            }
-            if (variant == 2) {
-                dz.zeros(256, c.st);
-                a.zeros = dz.p;
-            }
-        }
-        if (mrf_mode != 0) {
-            gm.upload(mrf, B, Cout, Lout, half && a.mrf_f16, guard_value);
-            a.mrf = reinterpret_cast<float*>(gm.data());
-        }
-        if (mrf_mode == 0 || mrf_mode == 3) {
-            go.upload(out, B, Cout, Lout, half && a.out_act_f16, guard_value);
-            a.out = reinterpret_cast<float*>(go.data());
-        }
-        if (half)
-            launch_conv1d_f16(a, KS, DIL, c.st);
-        else
-            launch_conv1d(a, KS, DIL, c.st);
-        long long bad = 0;
-        if (mrf_mode != 0) bad += gm.download(mrf, c.st);
-        if (mrf_mode == 0 || mrf_mode == 3) bad += go.download(out, c.st);
-        *guard_changed = bad;
+        *guard_changed = run_conv(c, variant_layout(variant), x, w, bias, cond, cond_row, cond_rows, cond_stride, res, mrf, out, lens, B, Cin, Mtot,
+                                  Cout, L, KS, DIL, padl, slope, ups_s, ups_p, mrf_mode, out_slope, guard_value);
     });
 }
 int aur_dbg_resblock_round_f16(aur_engine* e, const float* y, const void* w1, const void* w2, const float* b1, const float* b2,
@@ -699,16 +678,14 @@ int aur_dbg_resblock_round_f16(aur_engine* e, const float* y, const void* w1, co
         a.w1 = dw1.p; a.w2 = dw2.p; a.b1 = db1.as<float>(); a.b2 = db2.as<float>();
         a.base_len = dl.as<int>(); a.len_mul = 1;
         a.stride = L; a.bstride = (long)C * L;
-        a.C = C; a.mrf_mode = mrf_mode; a.e_slope = e_slope;
+        a.C = C;
         a.B = B; a.max_len = L;
         a.zeros = dz.p;
         const bool has_out = mrf_mode == 0 || mrf_mode == 3, aliased = has_out && out == y;
-        if (mrf_mode != 0) {
-            gm.upload(mrf, B, C, L, true, guard_value);
-            a.mrf = gm.data();
-        }
+        if (mrf_mode != 0) gm.upload(mrf, B, C, L, true, guard_value);
         if (has_out && !aliased) go.upload(out, B, C, L, true, guard_value);
-        if (has_out) (mrf_mode == 0 ? a.out : a.e_out) = aliased ? gy.data() : go.data();
+        void* dout = !has_out ? nullptr : aliased ? gy.data() : go.data();
+        round_outputs(a, mrf_mode, dout, mrf_mode != 0 ? gm.data() : nullptr, dout, e_slope);
         launch_resblock_round_f16(a, KS, DIL, c.st);
         long long bad = 0;
         if (mrf_mode != 0) bad += gm.download(mrf, c.st);

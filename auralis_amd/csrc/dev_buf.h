@@ -1,4 +1,4 @@
-// Host-only RAII wrappers of device and pinned host allocations, shared by every host translation unit.
+// Host-only RAII wrappers of device and pinned host allocations and the profilers' event pool, shared by every host translation unit.
 #pragma once
 #include <vector>
 
@@ -66,5 +66,24 @@ struct PinBuf {
         return reinterpret_cast<T*>(p);
     }
 };
+
+// A pair of timing events and what the launches between them are booked as: the profiled batches of the decode chain and the
+// vocoder's launches.
+struct ProfEvent {
+    hipEvent_t a, b;
+    double flops, bytes;   // of ALL the launches between the two events
+    int kind;    // decode profile: 0..4 = GEMM kind (aur_stats.gemm_kind_*), 5 = paged attention; vocoder: aur_stats.conv_class_*, -1 = a whole forward
+    int count;   // launches between the two events (decode profile batches)
+};
+// the next event pair of a pool that grows on demand and is reused from the start once its events have been collected
+inline ProfEvent& next_event(std::vector<ProfEvent>& pool, size_t& n_used) {
+    if (n_used == pool.size()) {
+        ProfEvent e{};
+        HIP_CHECK(hipEventCreate(&e.a));
+        HIP_CHECK(hipEventCreate(&e.b));
+        pool.push_back(e);
+    }
+    return pool[n_used++];
+}
 
 }  // namespace aur

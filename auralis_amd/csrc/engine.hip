@@ -24,7 +24,7 @@
 #include "abi_internal.h"
 #include "cond_net.h"
 #include "gpt_host.h"
-#include "vocoder_kernels.h"
+#include "voc_net.h"
 
 namespace aur {
 
@@ -117,12 +117,6 @@ struct Seq {
     bool cancel = false;   // aur_cancel: stop decoding at the next step, skip the vocoder
 };
 
-struct ConvLayer {
-    const float* wp = nullptr;
-    const float* bias = nullptr;
-    const void* wp16 = nullptr;
-};
-
 class Engine {
 public:
     Engine(const aur_config& c, int device) : cfg_(c), device_(device) {
@@ -183,9 +177,10 @@ public:
         for (int i = 2 * S - 1; i >= 0; --i) latpool_free_.push_back(i);
         ws_[0].st = st_;
         ws_[1].st = st2_;
-        xt_f16_ = cfg_.vocoder_fp16 != 0;   // fp16 storage of the ResBlock intermediates and residual stream (see ConvArgs)
-        if (const char* e = getenv("AUR_XT_F16")) xt_f16_ = xt_f16_ && atoi(e) != 0;
-        if (const char* e = getenv("AUR_CONV_DMA")) conv_dma_ = atoi(e) != 0;   // 0: register-staged ResBlock convs (A/B only)
+        VocLayout lay{cfg_.vocoder_fp16 != 0, cfg_.vocoder_fp16 != 0, true};
+        if (const char* e = getenv("AUR_XT_F16")) lay.halves = lay.halves && atoi(e) != 0;   // 0: fp32 ResBlock intermediates and residual stream (A/B only)
+        if (const char* e = getenv("AUR_CONV_DMA")) lay.dma = atoi(e) != 0;   // 0: register-staged ResBlock convs (A/B only)
+        voc_.reset(new HifiGan([this](const std::string& n) { return W(n); }, st_voc_, lay));
         if (const char* e = getenv("AUR_GEMM_PRESPLIT")) gemm_presplit_ = atoi(e) != 0; // 0: prompt-row GEMMs split their weights per tile instead of reading the planes packed at load time (A/B only)
         if (const char* e = getenv("AUR_DECODE_PIPELINE")) pipeline_ = atoi(e) != 0;
         if (const char* e = getenv("AUR_SAMPLER_FULL_SORT")) sampler_full_sort_ = atoi(e) != 0;
@@ -206,11 +201,10 @@ public:
         (void)hipSetDevice(device_);
         (void)hipStreamSynchronize(st_);
         (void)hipStreamSynchronize(st_voc_);
-        for (auto* v : {&conv_events_, &gemm_events_})
-            for (auto& e : *v) {
-                (void)hipEventDestroy(e.a);
-                (void)hipEventDestroy(e.b);
-            }
+        for (auto& e : gemm_events_) {
+            (void)hipEventDestroy(e.a);
+            (void)hipEventDestroy(e.b);
+        }
         (void)hipEventDestroy(ev_a_);
         (void)hipEventDestroy(ev_b_);
         for (int i = 0; i < 2; ++i) {
@@ -242,7 +236,7 @@ public:
             dst.numel = t[i].numel;
             dst.f16_eff = false;
         }
-        voc_ready_ = false;
+        voc_->unbind();
         gpt_ready_ = false;
         if (gpt_f16_) check_gpt_f16();
     }
@@ -476,12 +470,12 @@ public:
         float* dst = voc_cond_.as<float>() + (long)row * kCondStride;
         const float* g = spk_emb_.as<float>() + (long)row * 512;
         launch_gemv_rows(W("voc.cond_layer.w", 512 * 512), W("voc.cond_layer.b", 512), g, dst, 512, 512, 1, 0, 0, st_);
-        const int C[4] = {256, 128, 64, 32};
         int off = 512;
         for (int i = 0; i < 4; ++i) {
+            const int C = kVocChans[i];
             const std::string p = "voc.conds." + std::to_string(i);
-            launch_gemv_rows(W(p + ".w", (int64_t)C[i] * 512), W(p + ".b", C[i]), g, dst + off, C[i], 512, 1, 0, 0, st_);
-            off += C[i];
+            launch_gemv_rows(W(p + ".w", (int64_t)C * 512), W(p + ".b", C), g, dst + off, C, 512, 1, 0, 0, st_);
+            off += C;
         }
         HIP_CHECK(hipStreamSynchronize(st_));
         prefill_speaker_prefix(row);
@@ -674,8 +668,7 @@ public:
         just_finished_.clear();
         last_active_.clear();
         n_gemm_events_ = 0;
-        n_conv_events_ = 0;
-        voc_timed_ = false;
+        voc_->drop_events();
         std::lock_guard<std::mutex> lk(mu_);
         auto fail = [&](Seq* s) {
             for (int b : s->blocks) free_blocks_.push_back(b);
@@ -862,7 +855,7 @@ public:
     void vocode_host(const float* latents, const int* n_lat, const float* speed, int B, int t_max, uint64_t key, float* wav_out,
                      int64_t wav_stride, int* n_samples_out) {
         use();
-        ensure_voc();
+        voc_->bind();
         const int row = speaker_row(key, false);
         AUR_REQUIRE(row >= 0, "unknown speaker_key");
         AUR_REQUIRE(B >= 1 && t_max >= 1, "B, t_max");
@@ -881,10 +874,11 @@ public:
         HIP_CHECK(hipMemcpyAsync(tmp_lat_.p, latents, (size_t)B * t_max * kHidden * sizeof(float),
                                  hipMemcpyHostToDevice, st_voc_));
         tmp_wav_.ensure((size_t)B * max_samples * sizeof(float));
-        run_vocoder(B, nl, sp, tmp_lat_.as<float>(), (long)t_max * kHidden, nullptr, cond, tmp_wav_.as<float>(),
-                    max_samples);
+        voc_->forward(B, nl, sp, tmp_lat_.as<float>(), (long)t_max * kHidden, nullptr, cond, tmp_wav_.as<float>(), max_samples,
+                      voc_cond_.as<float>(), cfg_.profile != 0);
+        stats_.vocoder_batches++;
         HIP_CHECK(hipStreamSynchronize(st_voc_));
-        collect_conv_events();
+        voc_->collect(stats_);
         for (int b = 0; b < B; ++b) {
             const int ns = frames_for(stretched_rows(nl[b], sp[b])) * 256;
             HIP_CHECK(hipMemcpy(wav_out + (long)b * wav_stride, tmp_wav_.as<float>() + (long)b * max_samples,
@@ -1013,8 +1007,6 @@ private:
     static constexpr int kMelVocab = 1026;
     static constexpr int kHeadPad = 1088;         // mel_head columns padded to a multiple of 64
     static constexpr int kStartToken = 1024, kStopToken = 1025;
-    static constexpr long kCondStride = 1024;
-
     bool idle() {
         std::lock_guard<std::mutex> lk(mu_);
         if (!waiting_.empty() || !voc_queue_.empty() || voc_active_ || infl_.on) return false;
@@ -1024,13 +1016,6 @@ private:
     }
 
     // ------------------------------------------------------------------ GPT
-    struct ConvEvent {
-        hipEvent_t a, b;
-        double flops, bytes;   // of ALL the launches between the two events
-        bool used;
-        int kind;   // decode profile events: 0..4 = GEMM kind (aur_stats.gemm_kind_*), 5 = paged attention
-        int count;  // launches between the two events (decode profile batches; 1 for a vocoder conv)
-    };
     struct Linear {   // one entry of kLinears in one layer
         const float *w, *b;       // the loaded [K][N] matrix (aur_config.gpt_fp16: W'' once ensure_gpt has run) and bias
         const float *lnw, *lnb;   // gain and shift of the LayerNorm in front of it, or null
@@ -1095,7 +1080,7 @@ private:
         text_pos_ = W("text_pos");
         text_vocab_ = (int)(w_.at("text_emb").numel / H);
         text_positions_ = (int)(w_.at("text_pos").numel / H);
-        ensure_voc();
+        voc_->bind();
         gpt_ready_ = true;
     }
     void ensure_rows(RowWs& w, int M) {
@@ -1127,18 +1112,8 @@ private:
     // stream, K/V pages and latents of the sequences are not touched).  One pair per n_layer launches: the interval is the
     // launch-to-launch period a kernel-trace reports per kernel.  Algorithmic bytes of a GEMM launch: weights once + the activation
     // rows once + the output tile once (the residual epilogue reads and writes it).
-    // the next event pair of a pool that grows on demand and is reused from the start once its events have been collected
-    static ConvEvent& next_event(std::vector<ConvEvent>& pool, size_t& n_used) {
-        if (n_used == pool.size()) {
-            ConvEvent e{};
-            HIP_CHECK(hipEventCreate(&e.a));
-            HIP_CHECK(hipEventCreate(&e.b));
-            pool.push_back(e);
-        }
-        return pool[n_used++];
-    }
-    ConvEvent& prof_event(int kind, double flops, double bytes, int count) {
-        ConvEvent& ev = next_event(gemm_events_, n_gemm_events_);
+    ProfEvent& prof_event(int kind, double flops, double bytes, int count) {
+        ProfEvent& ev = next_event(gemm_events_, n_gemm_events_);
         ev.kind = kind;
         ev.flops = flops;
         ev.bytes = bytes;
@@ -1218,12 +1193,12 @@ private:
             GemmRowsEpi epi;
             decode_gemm_kind(kind, &ln, &epi);
             const GemmRowsArgs a0 = decode_gemm_args(w, 0, kind, M, true);
-            ConvEvent& ev = prof_event(kind, nl * 2.0 * a0.M * a0.N * a0.K, nl * gemm_alg_bytes(a0, epi), nl);
+            ProfEvent& ev = prof_event(kind, nl * 2.0 * a0.M * a0.N * a0.K, nl * gemm_alg_bytes(a0, epi), nl);
             HIP_CHECK(hipEventRecord(ev.a, w.st));
             for (int l = 0; l < nl; ++l) launch_gemm_rows(decode_gemm_args(w, l, kind, M, true), ln, epi, w.st);
             HIP_CHECK(hipEventRecord(ev.b, w.st));
             if (kind == 0) {   // attention of every layer: the step's q rows against each layer's real K/V pages
-                ConvEvent& ea = prof_event(5, nl * 4.0 * kHidden * step_kv_tokens_, nl * ((kv_half_ ? 4.0 : 8.0) * kHidden * step_kv_tokens_ + 8.0 * kHidden * M), nl);
+                ProfEvent& ea = prof_event(5, nl * 4.0 * kHidden * step_kv_tokens_, nl * ((kv_half_ ? 4.0 : 8.0) * kHidden * step_kv_tokens_ + 8.0 * kHidden * M), nl);
                 HIP_CHECK(hipEventRecord(ea.a, w.st));
                 for (int l = 0; l < nl; ++l)
                     launch_paged_attention(w.qbuf.as<float>(), kv_layer(l), w.row_meta.as<int>(), kMaxBlocks, prof_h_.as<float>(), M, w.st, mtt, kv_half_);
@@ -1232,7 +1207,7 @@ private:
         }
         {   // the mel head has one weight matrix: its replays are L2 / Infinity-Cache warm after the first (1 launch in 152)
             const GemmRowsArgs a0 = head_gemm_args(w, M, true);
-            ConvEvent& ev = prof_event(4, nl * 2.0 * a0.M * a0.N * a0.K, nl * gemm_alg_bytes(a0, kEpiBias), nl);
+            ProfEvent& ev = prof_event(4, nl * 2.0 * a0.M * a0.N * a0.K, nl * gemm_alg_bytes(a0, kEpiBias), nl);
             HIP_CHECK(hipEventRecord(ev.a, w.st));
             for (int l = 0; l < nl; ++l) launch_gemm_rows(a0, false, kEpiBias, w.st);
             HIP_CHECK(hipEventRecord(ev.b, w.st));
@@ -1266,7 +1241,7 @@ private:
         for (size_t i = 0; i < n_gemm_events_; ++i) {
             float ms = 0.f;
             HIP_CHECK(hipEventElapsedTime(&ms, gemm_events_[i].a, gemm_events_[i].b));
-            const ConvEvent& ev = gemm_events_[i];
+            const ProfEvent& ev = gemm_events_[i];
             if (ev.kind == 5) {
                 stats_.attn_ms += ms;
                 stats_.attn_bytes += ev.bytes;
@@ -1673,235 +1648,6 @@ private:
     }
 
     // ------------------------------------------------------------------ vocoder
-    void ensure_voc() {
-        if (voc_ready_) return;
-        const bool f16 = cfg_.vocoder_fp16 != 0;
-        auto layer = [&](const std::string& n) {
-            ConvLayer l;
-            l.wp = W("voc." + n + ".wp");
-            l.bias = W("voc." + n + ".bias");
-            if (f16) l.wp16 = W("voc16." + n + ".wp");
-            return l;
-        };
-        v_pre_ = layer("conv_pre");
-        for (int i = 0; i < 4; ++i) {
-            v_ups_[i] = layer("ups." + std::to_string(i));
-            for (int j = 0; j < 3; ++j)
-                for (int c = 0; c < 3; ++c) {
-                    const std::string p = "rb." + std::to_string(i * 3 + j) + ".";
-                    v_c1_[i][j][c] = layer(p + "c1." + std::to_string(c));
-                    v_c2_[i][j][c] = layer(p + "c2." + std::to_string(c));
-                }
-        }
-        v_post_ = W("voc.conv_post.w");
-        voc_ready_ = true;
-    }
-    // the event pair of the next profiled conv launch (nullptr when the engine does not profile)
-    ConvEvent* next_conv_event() { return cfg_.profile ? &next_event(conv_events_, n_conv_events_) : nullptr; }
-    void conv(ConvArgs& a, int KS, int DIL, double tot_in, double tot_out) {
-        ConvEvent* ev = next_conv_event();
-        if (ev) {
-            // class for the per-stage roofline: ResBlock convs by channel count (256 / 128 / 64 / 32 -> 0..3), everything
-            // else (conv_pre, the four transposed convs) -> 4
-            ev->kind = (a.ups_s == 0 && a.Cin == a.Cout) ? (a.Cout == 256 ? 0 : a.Cout == 128 ? 1 : a.Cout == 64 ? 2 : a.Cout == 32 ? 3 : 4) : 4;
-            ev->flops = 2.0 * a.Cin * KS * a.Mtot * tot_in;
-            // bytes in the dtype each tensor is actually stored in (the c1 -> c2 intermediate may be fp16)
-            const double mrf_b = a.mrf_f16 ? 2.0 : 4.0;
-            const double o_b = a.out_act_f16 ? 2.0 : 4.0;
-            const double out_b = a.mrf_mode == 0 ? o_b : a.mrf_mode == 1 ? mrf_b : a.mrf_mode == 2 ? 2.0 * mrf_b : mrf_b + o_b;
-            ev->bytes = (a.x_f16 ? 2.0 : 4.0) * a.Cin * tot_in + a.Cout * tot_out * (out_b + (a.res ? (a.res_f16 ? 2.0 : 4.0) : 0.0));
-            HIP_CHECK(hipEventRecord(ev->a, st_voc_));
-        }
-        if (cfg_.vocoder_fp16)
-            launch_conv1d_f16(a, KS, DIL, st_voc_);
-        else
-            launch_conv1d(a, KS, DIL, st_voc_);
-        if (ev) HIP_CHECK(hipEventRecord(ev->b, st_voc_));
-    }
-    void round_conv(RoundArgs& a, int KS, int DIL, double tot) {
-        ConvEvent* ev = next_conv_event();
-        if (ev) {
-            ev->kind = a.C == 64 ? 2 : 3;
-            ev->flops = 2.0 * (2.0 * a.C * KS * a.C * tot);   // conv1 + conv2
-            // stream in, then: stream out (mode 0) | running sum out (1) | in and out (2) | running sum in, stage output out (3)
-            const double io = a.mrf_mode == 0 ? 2.0 : a.mrf_mode == 1 ? 2.0 : 4.0;
-            ev->bytes = a.C * tot * (2.0 + io);
-            HIP_CHECK(hipEventRecord(ev->a, st_voc_));
-        }
-        launch_resblock_round_f16(a, KS, DIL, st_voc_);
-        if (ev) HIP_CHECK(hipEventRecord(ev->b, st_voc_));
-    }
-    void collect_conv_events() {
-        for (size_t i = 0; i < n_conv_events_; ++i) {
-            float ms = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&ms, conv_events_[i].a, conv_events_[i].b));
-            stats_.conv_ms += ms;
-            stats_.conv_flops += conv_events_[i].flops;
-            stats_.conv_bytes += conv_events_[i].bytes;
-            stats_.conv_launches++;
-            const int k = conv_events_[i].kind;
-            if (k >= 0 && k < 5) {
-                stats_.conv_class_ms[k] += ms;
-                stats_.conv_class_flops[k] += conv_events_[i].flops;
-                stats_.conv_class_bytes[k] += conv_events_[i].bytes;
-                stats_.conv_class_launches[k]++;
-            }
-        }
-        n_conv_events_ = 0;
-        if (voc_timed_) {
-            float ms = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&ms, ev_va_, ev_vb_));
-            stats_.vocoder_ms += ms;
-            voc_timed_ = false;
-        }
-    }
-    // latents: d_lat + lat_row[b]*lat_bstride (lat_row nullable => b); wav: d_wav + b*wav_bstride; speed[b] as aur_seq_desc.speed
-    void run_vocoder(int B, const std::vector<int>& n_lat, const std::vector<float>& speed, const float* d_lat, long lat_bstride,
-                     const std::vector<int>* lat_row, const std::vector<int>& cond_row, float* d_wav, long wav_bstride) {
-        ensure_voc();
-        if (!ev_va_) {
-            HIP_CHECK(hipEventCreate(&ev_va_));
-            HIP_CHECK(hipEventCreate(&ev_vb_));
-        }
-        std::vector<int>& meta = h_meta_;   // member: the async H2D copy below must not outlive its source
-        meta.assign(6 * (size_t)B, 0);
-        int maxT = 0;
-        double totT = 0;
-        bool stretched = false;   // some utterance's speed changes its row count: the three-stage kernel
-        for (int b = 0; b < B; ++b) {
-            const int l0 = stretched_rows(n_lat[b], speed[b]);
-            const float r0 = stretch_ratio(speed[b]);
-            meta[b] = n_lat[b];
-            meta[B + b] = frames_for(l0);
-            meta[2 * B + b] = cond_row[b];
-            meta[3 * B + b] = lat_row ? (*lat_row)[b] : b;
-            meta[4 * B + b] = l0;
-            std::memcpy(&meta[5 * B + b], &r0, 4);
-            stretched |= l0 != n_lat[b];
-            maxT = std::max(maxT, meta[B + b]);
-            totT += meta[B + b];
-        }
-        v_meta_.ensure(meta.size() * 4);
-        HIP_CHECK(hipMemcpyAsync(v_meta_.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st_voc_));
-        const int* d_nlat = v_meta_.as<int>();
-        const int* d_len = d_nlat + B;
-        const int* d_cond = d_nlat + 2 * B;
-        const int* d_latrow = d_nlat + 3 * B;
-        const size_t T = (size_t)maxT, Bz = (size_t)B;
-        v_z_.ensure(Bz * 1024 * T * 4);
-        v_s0_.ensure(Bz * 512 * T * 4);
-        for (auto* b : {&v_B_, &v_D_, &v_E_}) b->ensure(Bz * 8192 * T * 4);
-        if (!v_zero_.p) {
-            v_zero_.ensure(256);
-            HIP_CHECK(hipMemsetAsync(v_zero_.p, 0, 256, st_voc_));
-        }
-        if (xt_f16_) {   // the residual stream as activated halves (stage input, running value)
-            v_Ah_.ensure(Bz * 8192 * T * 2);
-            v_Ch_.ensure(Bz * 8192 * T * 2);
-            v_Ch2_.ensure(Bz * 8192 * T * 2);
-        } else {
-            v_A_.ensure(Bz * 8192 * T * 4);
-            v_C_.ensure(Bz * 8192 * T * 4);
-        }
-        HIP_CHECK(hipEventRecord(ev_va_, st_voc_));
-        // fp16 vocoder: z leaves the interpolation as interleaved halves (what conv_pre's staging rounded it to anyway) and conv_pre
-        // runs on the LDS-DMA kernel like every other wide conv (round 5: the register-staged kernel, with 32 spilled VGPRs)
-        const bool z_f16 = xt_f16_ && conv_dma_;
-        // (a batch in which every utterance keeps its rows -- speed 1, or a stretch that floors back to n_lat -- is the two-stage kernel's)
-        if (stretched)
-            launch_interp3(d_lat, lat_bstride, d_latrow, d_nlat, d_nlat + 4 * B, reinterpret_cast<const float*>(d_nlat + 5 * B), d_len,
-                           v_z_.as<float>(), (long)T, (long)(1024 * T), 1024, B, maxT, st_voc_, z_f16);
-        else
-            launch_interp2(d_lat, lat_bstride, d_latrow, d_nlat, d_len, v_z_.as<float>(), (long)T, (long)(1024 * T), 1024, B, maxT, st_voc_, z_f16);
-        const float* condt = voc_cond_.as<float>();
-        ConvArgs a{};
-        a.base_len = d_len; a.B = B; a.cond_row = d_cond; a.cond_stride = kCondStride;
-        // conv_pre (+ cond_layer)
-        a.x = v_z_.as<float>(); a.x_f16 = z_f16 ? 1 : 0; a.zeros = z_f16 ? v_zero_.p : nullptr;
-        a.wp = v_pre_.wp; a.wp16 = v_pre_.wp16; a.bias = v_pre_.bias; a.cond = condt; a.res = nullptr; a.mrf = nullptr;
-        a.out = v_s0_.as<float>(); a.len_mul = 1; a.Cin = 1024; a.Mtot = 512; a.Cout = 512;
-        a.x_stride = (long)T; a.o_stride = (long)T; a.x_bstride = (long)(1024 * T); a.o_bstride = (long)(512 * T);
-        a.padl = 3; a.slope = 1.0f; a.ups_s = 0; a.ups_p = 0; a.mrf_mode = 0; a.max_len = maxT;
-        // fp16 vocoder: every stage input (conv_pre's output, the MRF means) is stored the way its consumer stages it,
-        // fp16(lrelu(x, 0.1)) interleaved -- 0.01 for the last one, which feeds conv_post
-        if (xt_f16_) { a.out_act_f16 = 1; a.out_slope = 0.1f; }
-        conv(a, 7, 1, totT, totT);
-        const int rates[4] = {8, 8, 2, 2}, kern[4] = {16, 16, 4, 4}, chans[4] = {256, 128, 64, 32};
-        const int rk[3] = {3, 7, 11}, rd[3] = {1, 3, 5};
-        const float* in = v_s0_.as<float>();
-        int Cin = 512, mul = 1, cond_off = 512;
-        float *A = v_A_.as<float>(), *Bb = v_B_.as<float>(), *Cb = v_C_.as<float>(), *D = v_D_.as<float>(), *E = v_E_.as<float>();
-        void *Ah = v_Ah_.p, *Ch = v_Ch_.p, *Ch2 = v_Ch2_.p;   // fp16 vocoder: the activated residual stream (stage input / after rounds 0, 1)
-        for (int i = 0; i < 4; ++i) {
-            const int s = rates[i], C = chans[i], mul_out = mul * s;
-            const long Lin = (long)T * mul, Lout = (long)T * mul_out;
-            // transposed conv as 2-tap polyphase conv over virtual channels co*s + r
-            a = ConvArgs{};
-            a.base_len = d_len; a.B = B; a.cond_row = d_cond; a.cond_stride = kCondStride;
-            a.x = in; a.x_f16 = xt_f16_ ? 1 : 0; a.zeros = (xt_f16_ && conv_dma_) ? v_zero_.p : nullptr; a.wp = v_ups_[i].wp; a.wp16 = v_ups_[i].wp16; a.bias = v_ups_[i].bias; a.cond = condt + cond_off; a.out = A;
-            a.len_mul = mul; a.Cin = Cin; a.Mtot = C * s; a.Cout = C;
-            a.x_stride = Lin; a.x_bstride = (long)Cin * Lin; a.o_stride = Lout; a.o_bstride = (long)C * Lout;
-            a.padl = 1; a.slope = 0.1f; a.ups_s = s; a.ups_p = (kern[i] - s) / 2; a.mrf_mode = 0; a.max_len = maxT * mul;
-            if (xt_f16_) { a.out = reinterpret_cast<float*>(Ah); a.out_act_f16 = 1; a.out_slope = 0.1f; }
-            conv(a, 2, 1, totT * mul, totT * mul_out);
-            cond_off += C;
-            // the 64- and 32-channel stages (HBM-bound as two launches per round): one fused launch per ResBlock round, the
-            // conv1 -> conv2 intermediate stays in LDS and the residual comes from the staged window (vocoder_kernels.h, RoundArgs);
-            // the stream ping-pongs Ah -> Ch -> Ch2 because neighbouring tiles read each other's halo
-            const bool fused = xt_f16_ && conv_dma_ && C <= 64;
-            for (int j = 0; j < 3 && fused; ++j)
-                for (int c = 0; c < 3; ++c) {
-                    RoundArgs ra{};
-                    ra.y = (c == 0) ? Ah : (c == 1) ? Ch : Ch2;
-                    ra.out = (c == 0) ? Ch : (c == 1) ? Ch2 : nullptr;
-                    ra.w1 = v_c1_[i][j][c].wp16; ra.w2 = v_c2_[i][j][c].wp16; ra.b1 = v_c1_[i][j][c].bias; ra.b2 = v_c2_[i][j][c].bias;
-                    ra.base_len = d_len; ra.len_mul = mul_out; ra.stride = Lout; ra.bstride = (long)C * Lout; ra.C = C;
-                    ra.B = B; ra.max_len = maxT * mul_out; ra.zeros = v_zero_.p;
-                    if (c == 2) {
-                        ra.mrf = D; ra.e_out = E; ra.mrf_mode = (j == 0) ? 1 : (j == 1) ? 2 : 3;
-                        ra.e_slope = (i == 3) ? 0.01f : 0.1f;
-                    }
-                    round_conv(ra, rk[j], rd[c], totT * mul_out);
-                }
-            for (int j = 0; j < 3 && !fused; ++j)
-                for (int c = 0; c < 3; ++c) {
-                    // fp16 vocoder: the residual stream of a ResBlock lives in HBM as activated interleaved halves, fp16(lrelu(x)):
-                    // Ah (the transposed conv's output, shared by the stage's three ResBlocks) in round 0, Ch (updated in place by
-                    // the residual convs) afterwards.  First convs stage it as is; residual convs read it back and undo the
-                    // activation (ConvArgs::res_f16).  fp32 vocoder: A / Cb, fp32.
-                    const float* r = xt_f16_ ? reinterpret_cast<const float*>(c == 0 ? Ah : Ch) : (c == 0 ? A : Cb);
-                    ConvArgs b1{};
-                    b1.base_len = d_len; b1.B = B;
-                    b1.x = r; b1.x_f16 = xt_f16_ ? 1 : 0; b1.zeros = conv_dma_ ? v_zero_.p : nullptr;
-                    b1.wp = v_c1_[i][j][c].wp; b1.wp16 = v_c1_[i][j][c].wp16; b1.bias = v_c1_[i][j][c].bias; b1.out = Bb;
-                    b1.len_mul = mul_out; b1.Cin = C; b1.Mtot = C; b1.Cout = C;
-                    b1.x_stride = Lout; b1.o_stride = Lout; b1.x_bstride = (long)C * Lout; b1.o_bstride = (long)C * Lout;
-                    b1.padl = (rk[j] - 1) / 2 * rd[c]; b1.slope = 0.1f; b1.max_len = maxT * mul_out;
-                    if (xt_f16_) { b1.out_act_f16 = 1; b1.out_slope = 0.1f; }   // c1 -> c2 intermediate: fp16(lrelu(.)), what c2 stages anyway
-                    conv(b1, rk[j], rd[c], totT * mul_out, totT * mul_out);
-                    ConvArgs b2 = b1;
-                    b2.out_act_f16 = 0;
-                    b2.x = Bb; b2.wp = v_c2_[i][j][c].wp; b2.wp16 = v_c2_[i][j][c].wp16; b2.bias = v_c2_[i][j][c].bias;
-                    b2.res = r;
-                    if (xt_f16_) { b2.res_f16 = 1; b2.res_unact = 1.0f / 0.1f; }
-                    b2.padl = (rk[j] - 1) / 2;
-                    if (c < 2) {
-                        if (xt_f16_) { b2.out = reinterpret_cast<float*>(Ch); b2.out_act_f16 = 1; b2.out_slope = 0.1f; }
-                        else b2.out = Cb;
-                    } else {
-                        b2.mrf = D; b2.out = E; b2.mrf_mode = (j == 0) ? 1 : (j == 1) ? 2 : 3;
-                        b2.mrf_f16 = xt_f16_ ? 1 : 0;   // D: running sum of the three ResBlock outputs (halves in fp16 mode)
-                        if (xt_f16_ && j == 2) { b2.out_act_f16 = 1; b2.out_slope = (i == 3) ? 0.01f : 0.1f; }   // E: the next stage's input
-                    }
-                    conv(b2, rk[j], 1, totT * mul_out, totT * mul_out);
-                }
-            in = E; Cin = C; mul = mul_out;
-        }
-        launch_conv_post(E, v_post_, d_wav, d_len, 256, 32, (long)T * 256, (long)32 * T * 256, wav_bstride, 0.01f, B, maxT * 256, st_voc_, xt_f16_);
-        HIP_CHECK(hipEventRecord(ev_vb_, st_voc_));
-        voc_timed_ = true;
-        stats_.vocoder_batches++;
-    }
     void voc_launch() {
         // The workspace is B x maxT and a slowed utterance is up to twice as long (aur_seq_desc.speed): a pass takes the longest prefix
         // of the queue with B * maxT <= max_seqs * frames_for(kMaxLatRows), today's worst case; a single utterance is always admissible
@@ -1950,7 +1696,9 @@ private:
         // decode step being over).  hipHostMalloc memory is device-visible and coherent; the event below orders the host's reads.
         float* hw = voc_block_->buf.as<float>();
         float* hl = hw + (size_t)B * voc_max_samples_;
-        run_vocoder(B, voc_nl_, voc_speed_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_);
+        voc_->forward(B, voc_nl_, voc_speed_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_,
+                      voc_cond_.as<float>(), cfg_.profile != 0);
+        stats_.vocoder_batches++;
         for (int b = 0; b < B && cfg_.return_latents; ++b)
             HIP_CHECK(hipMemcpyAsync(hl + (size_t)b * kMaxLatRows * kHidden,
                                      latpool_.as<float>() + (long)rows[b] * kMaxLatRows * kHidden,
@@ -1968,7 +1716,7 @@ private:
             if (q == hipErrorNotReady) return;
             HIP_CHECK(q);
         }
-        collect_conv_events();
+        voc_->collect(stats_);
         const int B = (int)voc_batch_.size();
         const float* hw = voc_block_->buf.as<float>();
         const float* hl = hw + (size_t)B * voc_max_samples_;
@@ -2004,10 +1752,9 @@ private:
     aur_config cfg_;
     int device_;
     hipStream_t st_ = nullptr;
-    hipEvent_t ev_a_ = nullptr, ev_b_ = nullptr, ev_va_ = nullptr, ev_vb_ = nullptr;
-    bool voc_timed_ = false;
+    hipEvent_t ev_a_ = nullptr, ev_b_ = nullptr;
     std::unordered_map<std::string, Tensor> w_;
-    bool gpt_ready_ = false, voc_ready_ = false;
+    bool gpt_ready_ = false;
     std::vector<LayerW> layers_;
     std::vector<std::unique_ptr<DevBuf>> packed_;   // pack_wt16 copies (decode GEMM layout)
     DevBuf fold_scratch_;                           // load-time scratch of launch_fold_ln
@@ -2070,19 +1817,14 @@ private:
     bool host_trace_ = false;           // AUR_HOST_TRACE=1: host time of enqueueing a decode step vs waiting for the previous one (stderr, every 256 steps)
     long ht_launch_ns_ = 0, ht_wait_ns_ = 0, ht_n_ = 0;
     bool pipeline_ = true;              // AUR_DECODE_PIPELINE=0: wait for every read-back before launching the next step
-    bool conv_dma_ = true;              // ResBlock convs of the fp16 vocoder on the LDS-DMA staged kernel
-    bool xt_f16_ = false;               // set in the constructor: fp16 vocoder => fp16 c1 -> c2 intermediate (AUR_XT_F16=0 disables)
     std::vector<int> last_active_;      // live slots whose row indices are resident in the decode chain's index buffers
     hipStream_t st2_ = nullptr;
     DevBuf i_init_;
     DevBuf dbg_lnf_, dbg_logits_;
     bool dbg_capture_ = false;
-    // vocoder
-    ConvLayer v_pre_, v_ups_[4], v_c1_[4][3][3], v_c2_[4][3][3];
-    const float* v_post_ = nullptr;
-    DevBuf v_meta_, v_z_, v_s0_, v_A_, v_B_, v_C_, v_D_, v_E_, v_Ch_, v_Ch2_, v_Ah_, v_zero_, tmp_lat_, tmp_wav_;
-    std::vector<ConvEvent> conv_events_;
-    std::vector<ConvEvent> gemm_events_;
+    std::unique_ptr<HifiGan> voc_;      // the vocoder's forward graph, weights tables, workspace and profile events (voc_net.h)
+    DevBuf tmp_lat_, tmp_wav_;          // vocode_host's device copies
+    std::vector<ProfEvent> gemm_events_;
     size_t n_gemm_events_ = 0;
     int profile_every_ = kProfileEvery;
     DevBuf prof_q_, prof_h_, prof_stats_, prof_act_, prof_kv_;   // output scratch of profile_replay
@@ -2091,8 +1833,6 @@ private:
     double step_kv_tokens_ = 0.0;       // sum of context lengths of the step being launched (profile accounting)
     long decode_step_count_ = 0;
     float event_overhead_ms_ = -1.f;
-    std::vector<int> h_meta_;
-    size_t n_conv_events_ = 0;
     // sequences
     std::mutex mu_;
     uint64_t next_id_ = 1;

@@ -506,21 +506,35 @@ static void launch_conv_mt(const ConvArgs& a, hipStream_t st) {
         launch_conv_t<KS, DIL, 32, CK>(a, st);
 }
 
-void launch_conv1d(const ConvArgs& a, int KS, int DIL, hipStream_t st) {
-    const int key = KS * 16 + DIL;
-    switch (key) {
-        case 2 * 16 + 1: launch_conv_mt<2, 1, 16>(a, st); break;
-        case 3 * 16 + 1: launch_conv_mt<3, 1, 16>(a, st); break;
-        case 3 * 16 + 3: launch_conv_mt<3, 3, 16>(a, st); break;
-        case 3 * 16 + 5: launch_conv_mt<3, 5, 16>(a, st); break;
-        case 7 * 16 + 1: launch_conv_mt<7, 1, 8>(a, st); break;
-        case 7 * 16 + 3: launch_conv_mt<7, 3, 8>(a, st); break;
-        case 7 * 16 + 5: launch_conv_mt<7, 5, 8>(a, st); break;
-        case 11 * 16 + 1: launch_conv_mt<11, 1, 4>(a, st); break;
-        case 11 * 16 + 3: launch_conv_mt<11, 3, 4>(a, st); break;
-        case 11 * 16 + 5: launch_conv_mt<11, 5, 4>(a, st); break;
-        default: throw InvalidArgument("launch_conv1d: unsupported (kernel,dilation)");
+// The (taps, dilation) pairs the vocoder runs -- k = 2 for the polyphase transposed convs, the ResBlocks' {3, 7, 11} x {1, 3, 5} -- as
+// compile-time constants: returns f(integral_constant KS, integral_constant DIL), false for any other pair (the launcher words the error).
+template <class F>
+static bool dispatch_taps(int KS, int DIL, F&& f) {
+    using i1 = std::integral_constant<int, 1>;
+    using i3 = std::integral_constant<int, 3>;
+    using i5 = std::integral_constant<int, 5>;
+    switch (KS * 16 + DIL) {
+        case 2 * 16 + 1: return f(std::integral_constant<int, 2>{}, i1{});
+        case 3 * 16 + 1: return f(i3{}, i1{});
+        case 3 * 16 + 3: return f(i3{}, i3{});
+        case 3 * 16 + 5: return f(i3{}, i5{});
+        case 7 * 16 + 1: return f(std::integral_constant<int, 7>{}, i1{});
+        case 7 * 16 + 3: return f(std::integral_constant<int, 7>{}, i3{});
+        case 7 * 16 + 5: return f(std::integral_constant<int, 7>{}, i5{});
+        case 11 * 16 + 1: return f(std::integral_constant<int, 11>{}, i1{});
+        case 11 * 16 + 3: return f(std::integral_constant<int, 11>{}, i3{});
+        case 11 * 16 + 5: return f(std::integral_constant<int, 11>{}, i5{});
+        default: return false;
     }
+}
+
+void launch_conv1d(const ConvArgs& a, int KS, int DIL, hipStream_t st) {
+    const bool ok = dispatch_taps(KS, DIL, [&](auto k, auto d) {
+        constexpr int K = decltype(k)::value, D = decltype(d)::value;
+        launch_conv_mt<K, D, (K <= 3 ? 16 : K == 7 ? 8 : 4)>(a, st);   // input channels per staged chunk
+        return true;
+    });
+    if (!ok) throw InvalidArgument("launch_conv1d: unsupported (kernel,dilation)");
     HIP_CHECK(hipGetLastError());
 }
 
@@ -1030,18 +1044,12 @@ static void launch_round_c(const RoundArgs& a, hipStream_t st) {
 void launch_resblock_round_f16(const RoundArgs& a, int KS, int DIL, hipStream_t st) {
     AUR_REQUIRE(a.y && a.zeros && a.w1 && a.w2 && a.b1 && a.b2, "resblock round: arguments");
     AUR_REQUIRE(a.mrf_mode == 0 ? (a.out && a.out != a.y) : (a.mrf && (a.mrf_mode != 3 || a.e_out)), "resblock round: outputs of the mode");
-    switch (KS * 16 + DIL) {
-        case 3 * 16 + 1: launch_round_c<3, 1>(a, st); break;
-        case 3 * 16 + 3: launch_round_c<3, 3>(a, st); break;
-        case 3 * 16 + 5: launch_round_c<3, 5>(a, st); break;
-        case 7 * 16 + 1: launch_round_c<7, 1>(a, st); break;
-        case 7 * 16 + 3: launch_round_c<7, 3>(a, st); break;
-        case 7 * 16 + 5: launch_round_c<7, 5>(a, st); break;
-        case 11 * 16 + 1: launch_round_c<11, 1>(a, st); break;
-        case 11 * 16 + 3: launch_round_c<11, 3>(a, st); break;
-        case 11 * 16 + 5: launch_round_c<11, 5>(a, st); break;
-        default: throw InvalidArgument("resblock round: k in {3,7,11}, dilation in {1,3,5}");
-    }
+    const bool ok = dispatch_taps(KS, DIL, [&](auto k, auto d) {
+        constexpr int K = decltype(k)::value, D = decltype(d)::value;
+        if constexpr (K != 2) launch_round_c<K, D>(a, st);   // (k = 2 is the transposed convs': no fused round of it exists)
+        return K != 2;
+    });
+    if (!ok) throw InvalidArgument("resblock round: k in {3,7,11}, dilation in {1,3,5}");
     HIP_CHECK(hipGetLastError());
 }
 
@@ -1068,54 +1076,19 @@ static void launch_conv_f16_t(const ConvArgs& a, hipStream_t st) {
 
 void launch_conv1d_f16(const ConvArgs& a, int KS, int DIL, hipStream_t st) {
     // fp16 interleaved inputs (every ResBlock conv): LDS-DMA staged, multi-buffered for 64-channel output tiles; the 32-channel
-    // stage (2 chunks per tile, HBM-bound) measured faster register-staged (37.7 vs 40.4 ms per 3 batches)
-    if (a.x_f16 && a.zeros && a.Mtot % 64 == 0) {
-        switch (KS * 16 + DIL) {
-            case 2 * 16 + 1: launch_conv_dma<2, 1>(a, st); break;
-            case 3 * 16 + 1: launch_conv_dma<3, 1>(a, st); break;
-            case 3 * 16 + 3: launch_conv_dma<3, 3>(a, st); break;
-            case 3 * 16 + 5: launch_conv_dma<3, 5>(a, st); break;
-            case 7 * 16 + 1: launch_conv_dma<7, 1>(a, st); break;
-            case 7 * 16 + 3: launch_conv_dma<7, 3>(a, st); break;
-            case 7 * 16 + 5: launch_conv_dma<7, 5>(a, st); break;
-            case 11 * 16 + 1: launch_conv_dma<11, 1>(a, st); break;
-            case 11 * 16 + 3: launch_conv_dma<11, 3>(a, st); break;
-            case 11 * 16 + 5: launch_conv_dma<11, 5>(a, st); break;
-            default: throw InvalidArgument("launch_conv1d_f16: fp16 input only for k in {3,7,11}, dilation in {1,3,5}");
-        }
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (a.x_f16) {   // same inputs, register-staged (32-channel stage, transposed convs; no zero page given: tools/conv_diag's reference point)
-        switch (KS * 16 + DIL) {
-            case 2 * 16 + 1: launch_conv_f16_t<2, 1, true>(a, st); break;
-            case 3 * 16 + 1: launch_conv_f16_t<3, 1, true>(a, st); break;
-            case 3 * 16 + 3: launch_conv_f16_t<3, 3, true>(a, st); break;
-            case 3 * 16 + 5: launch_conv_f16_t<3, 5, true>(a, st); break;
-            case 7 * 16 + 1: launch_conv_f16_t<7, 1, true>(a, st); break;
-            case 7 * 16 + 3: launch_conv_f16_t<7, 3, true>(a, st); break;
-            case 7 * 16 + 5: launch_conv_f16_t<7, 5, true>(a, st); break;
-            case 11 * 16 + 1: launch_conv_f16_t<11, 1, true>(a, st); break;
-            case 11 * 16 + 3: launch_conv_f16_t<11, 3, true>(a, st); break;
-            case 11 * 16 + 5: launch_conv_f16_t<11, 5, true>(a, st); break;
-            default: throw InvalidArgument("launch_conv1d_f16: fp16 input only for k in {3,7,11}, dilation in {1,3,5}");
-        }
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    switch (KS * 16 + DIL) {
-        case 2 * 16 + 1: launch_conv_f16_t<2, 1, false>(a, st); break;
-        case 3 * 16 + 1: launch_conv_f16_t<3, 1, false>(a, st); break;
-        case 3 * 16 + 3: launch_conv_f16_t<3, 3, false>(a, st); break;
-        case 3 * 16 + 5: launch_conv_f16_t<3, 5, false>(a, st); break;
-        case 7 * 16 + 1: launch_conv_f16_t<7, 1, false>(a, st); break;
-        case 7 * 16 + 3: launch_conv_f16_t<7, 3, false>(a, st); break;
-        case 7 * 16 + 5: launch_conv_f16_t<7, 5, false>(a, st); break;
-        case 11 * 16 + 1: launch_conv_f16_t<11, 1, false>(a, st); break;
-        case 11 * 16 + 3: launch_conv_f16_t<11, 3, false>(a, st); break;
-        case 11 * 16 + 5: launch_conv_f16_t<11, 5, false>(a, st); break;
-        default: throw InvalidArgument("launch_conv1d_f16: unsupported (kernel,dilation)");
-    }
+    // stage (2 chunks per tile, HBM-bound) measured faster register-staged (37.7 vs 40.4 ms per 3 batches).  Without a zero page the
+    // same inputs are register-staged (32-channel stage, transposed convs; tools/conv_diag's reference point).
+    const bool dma = a.x_f16 && a.zeros && a.Mtot % 64 == 0;
+    const bool ok = dispatch_taps(KS, DIL, [&](auto k, auto d) {
+        constexpr int K = decltype(k)::value, D = decltype(d)::value;
+        if (dma) launch_conv_dma<K, D>(a, st);
+        else if (a.x_f16) launch_conv_f16_t<K, D, true>(a, st);
+        else launch_conv_f16_t<K, D, false>(a, st);
+        return true;
+    });
+    if (!ok)
+        throw InvalidArgument(a.x_f16 ? "launch_conv1d_f16: fp16 input only for k in {3,7,11}, dilation in {1,3,5}"
+                                      : "launch_conv1d_f16: unsupported (kernel,dilation)");
     HIP_CHECK(hipGetLastError());
 }
 
@@ -1135,101 +1108,6 @@ __device__ __forceinline__ void lin_src(float r, int j, int L, int& i0, int& i1,
 // compared bit for bit)
 __device__ __forceinline__ float lerp_f(float a, float b, float lam) { return fmaf(lam, b, (1.0f - lam) * a); }
 
-__global__ __launch_bounds__(256) void interp2_kernel(const float* __restrict__ lat, long lat_bstride,
-                                                      const int* __restrict__ lat_row,
-                                                      const int* __restrict__ n_lat,
-                                                      const int* __restrict__ base_len, float* __restrict__ z,
-                                                      long z_stride, long z_bstride, int C, float r1, float r2) {
-    const int b = blockIdx.z;
-    const int c = blockIdx.y;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    const int L0 = n_lat[b];
-    const int L1 = 4 * L0;
-    const int L2 = base_len[b];
-    if (j >= L2) return;
-    const float* x = lat + (long)(lat_row ? lat_row[b] : b) * lat_bstride + c;   // x[k] = x[k*C]
-    int i0, i1;
-    float lam2;
-    lin_src(r2, j, L1, i0, i1, lam2);
-    if (L2 == L1) {   // n_lat <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
-        i0 = i1 = j;
-        lam2 = 0.f;
-    }
-    float y[2];
-    const int idx[2] = {i0, i1};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        int k0, k1;
-        float lam1;
-        lin_src(r1, idx[u], L0, k0, k1, lam1);
-        y[u] = lerp_f(x[(long)k0 * C], x[(long)k1 * C], lam1);
-    }
-    z[(long)b * z_bstride + (long)c * z_stride + j] = lerp_f(y[0], y[1], lam2);
-}
-
-// The same values as interleaved halves z16[b][C/16][z_stride][16] = fp16(z) -- what conv_pre's staging rounds the fp32 z to anyway
-// (its input activation is the identity), so conv_pre can take the LDS-DMA kernel on bit-identical MFMA operands.  A thread = eight
-// channels of one position: 32 contiguous bytes of each of the (at most four) latent rows it blends, one 16-byte store.
-__global__ __launch_bounds__(256) void interp2_h_kernel(const float* __restrict__ lat, long lat_bstride, const int* __restrict__ lat_row,
-                                                        const int* __restrict__ n_lat, const int* __restrict__ base_len,
-                                                        _Float16* __restrict__ z, long z_stride, long z_bstride, int C, float r1, float r2) {
-    const int b = blockIdx.z;
-    const int c8 = blockIdx.y * 8;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    const int L0 = n_lat[b];
-    const int L1 = 4 * L0;
-    const int L2 = base_len[b];
-    if (j >= L2) return;
-    const float* x = lat + (long)(lat_row ? lat_row[b] : b) * lat_bstride + c8;
-    int i0, i1;
-    float lam2;
-    lin_src(r2, j, L1, i0, i1, lam2);
-    if (L2 == L1) {   // n_lat <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
-        i0 = i1 = j;
-        lam2 = 0.f;
-    }
-    const int idx[2] = {i0, i1};
-    float y[2][8];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        int k0, k1;
-        float lam1;
-        lin_src(r1, idx[u], L0, k0, k1, lam1);
-        const f32x4 a0 = *reinterpret_cast<const f32x4*>(x + (long)k0 * C), a1 = *reinterpret_cast<const f32x4*>(x + (long)k0 * C + 4);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(x + (long)k1 * C), b1 = *reinterpret_cast<const f32x4*>(x + (long)k1 * C + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y[u][e] = lerp_f(a0[e], b0[e], lam1);
-            y[u][e + 4] = lerp_f(a1[e], b1[e], lam1);
-        }
-    }
-    h16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (_Float16)lerp_f(y[0][e], y[1][e], lam2);
-    *reinterpret_cast<h16x8*>(z + (long)b * z_bstride + ((long)(c8 >> 4) * z_stride + j) * 16 + (c8 & 15)) = o;
-}
-
-void launch_interp2(const float* lat, long lat_bstride, const int* lat_row, const int* n_lat, const int* base_len, float* z,
-                    long z_stride, long z_bstride, int C, int B, int max_len, hipStream_t st, bool out_f16) {
-    const float r1 = (float)(1.0 / (1024.0 / 256.0));
-    const float r2 = (float)(1.0 / (24000.0 / 22050.0));
-    if (out_f16) {
-        AUR_REQUIRE(C % 16 == 0, "interp2: whole 16-channel chunks for the interleaved fp16 output");
-        dim3 grid((max_len + 255) / 256, C / 8, B);
-        trace_launch("interp2_h_kernel");
-        hipLaunchKernelGGL(interp2_h_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, base_len,
-                           reinterpret_cast<_Float16*>(z), z_stride, z_bstride, C, r1, r2);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    dim3 grid((max_len + 255) / 256, C, B);
-    trace_launch("interp2_kernel");
-    hipLaunchKernelGGL(interp2_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, base_len, z, z_stride,
-                       z_bstride, C, r1, r2);
-    HIP_CHECK(hipGetLastError());
-}
-
-// ------------------------------------------------------------------------------------------------
 // Speed control: a third linear interpolation at the head of the chain (aur_seq_desc.speed; the XTTS inference(speed=) rule,
 // F.interpolate(latents^T, scale_factor = 1/speed, mode="linear") ahead of HiFi-GAN).  Utterance b's n_lat[b] rows are stretched to
 // l0s[b] = stretched_rows(n_lat[b], speed[b]) rows with scale r0s[b]; the two stages above then run on l0s[b] rows.  Row s of the
@@ -1244,118 +1122,141 @@ __device__ __forceinline__ void stretch_src(float r0, int s, int n, int L0, int&
     }
 }
 
-// Same thread mapping and stores as interp2_kernel; an output position blends up to eight latent rows, innermost stage first.
+// One body for the four kernels below.  A thread is one output position j of utterance blockIdx.z: it blends two rows of the x4
+// sequence, each from two rows of the (stretched) latents, each of those -- STRETCH -- from two latent rows, innermost stage first.
+// HALF = false: one channel, z[b][c][j] fp32.  HALF = true: eight channels -- 32 contiguous bytes of every latent row it blends -- and
+// one 16-byte store into the interleaved halves z16[b][C/16][z_stride][16] = fp16(z), what conv_pre's staging rounds the fp32 z to
+// anyway (its input activation is the identity), so conv_pre can take the LDS-DMA kernel on bit-identical MFMA operands.
+// STRETCH = false: the latents are the rows as they are; l0s and r0s are not touched.
+template <bool STRETCH, bool HALF>
+__device__ __forceinline__ void interp_body(const float* __restrict__ lat, long lat_bstride, const int* __restrict__ lat_row,
+                                            const int* __restrict__ n_lat, const int* __restrict__ l0s, const float* __restrict__ r0s,
+                                            const int* __restrict__ base_len, void* __restrict__ z, long z_stride, long z_bstride, int C,
+                                            float r1, float r2) {
+    constexpr int NC = HALF ? 8 : 1;
+    const int b = blockIdx.z;
+    const int c = blockIdx.y * NC;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int n = n_lat[b];
+    int L0 = n;
+    if constexpr (STRETCH) L0 = l0s[b];
+    const int L1 = 4 * L0;
+    const int L2 = base_len[b];
+    if (j >= L2) return;
+    float r0 = 0.f;
+    if constexpr (STRETCH) r0 = r0s[b];
+    const float* x = lat + (long)(lat_row ? lat_row[b] : b) * lat_bstride + c;   // row k, channel c + e: x[k*C + e]
+    auto row = [&](int k, float (&v)[NC]) {
+        if constexpr (HALF) {
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(x + (long)k * C), hi = *reinterpret_cast<const f32x4*>(x + (long)k * C + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = lo[e];
+                v[e + 4] = hi[e];
+            }
+        } else {
+            v[0] = x[(long)k * C];
+        }
+    };
+    auto blend = [&](int k0, int k1, float lam, auto&& src, float (&v)[NC]) {   // v = lerp(src(k0), src(k1), lam)
+        float p[NC], q[NC];
+        src(k0, p);
+        src(k1, q);
+#pragma unroll
+        for (int e = 0; e < NC; ++e) v[e] = lerp_f(p[e], q[e], lam);
+    };
+    auto stretched = [&](int s, float (&v)[NC]) {   // row s of the stretched latents
+        if constexpr (STRETCH) {
+            int k0, k1;
+            float lam0;
+            stretch_src(r0, s, n, L0, k0, k1, lam0);
+            blend(k0, k1, lam0, row, v);
+        } else {
+            row(s, v);
+        }
+    };
+    auto x4 = [&](int i, float (&v)[NC]) {   // row i of the x4 sequence
+        int s0, s1;
+        float lam1;
+        lin_src(r1, i, L0, s0, s1, lam1);
+        blend(s0, s1, lam1, stretched, v);
+    };
+    int i0, i1;
+    float lam2;
+    lin_src(r2, j, L1, i0, i1, lam2);
+    if (L2 == L1) {   // L0 <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
+        i0 = i1 = j;
+        lam2 = 0.f;
+    }
+    float o[NC];
+    blend(i0, i1, lam2, x4, o);
+    if constexpr (HALF) {
+        h16x8 oh;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) oh[e] = (_Float16)o[e];
+        *reinterpret_cast<h16x8*>(static_cast<_Float16*>(z) + (long)b * z_bstride + ((long)(c >> 4) * z_stride + j) * 16 + (c & 15)) = oh;
+    } else {
+        static_cast<float*>(z)[(long)b * z_bstride + (long)c * z_stride + j] = o[0];
+    }
+}
+
+__global__ __launch_bounds__(256) void interp2_kernel(const float* __restrict__ lat, long lat_bstride,
+                                                      const int* __restrict__ lat_row,
+                                                      const int* __restrict__ n_lat,
+                                                      const int* __restrict__ base_len, float* __restrict__ z,
+                                                      long z_stride, long z_bstride, int C, float r1, float r2) {
+    interp_body<false, false>(lat, lat_bstride, lat_row, n_lat, nullptr, nullptr, base_len, z, z_stride, z_bstride, C, r1, r2);
+}
+__global__ __launch_bounds__(256) void interp2_h_kernel(const float* __restrict__ lat, long lat_bstride, const int* __restrict__ lat_row,
+                                                        const int* __restrict__ n_lat, const int* __restrict__ base_len,
+                                                        _Float16* __restrict__ z, long z_stride, long z_bstride, int C, float r1, float r2) {
+    interp_body<false, true>(lat, lat_bstride, lat_row, n_lat, nullptr, nullptr, base_len, z, z_stride, z_bstride, C, r1, r2);
+}
 __global__ __launch_bounds__(256) void interp3_kernel(const float* __restrict__ lat, long lat_bstride, const int* __restrict__ lat_row,
                                                       const int* __restrict__ n_lat, const int* __restrict__ l0s,
                                                       const float* __restrict__ r0s, const int* __restrict__ base_len,
                                                       float* __restrict__ z, long z_stride, long z_bstride, int C, float r1, float r2) {
-    const int b = blockIdx.z;
-    const int c = blockIdx.y;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    const int n = n_lat[b];
-    const int L0 = l0s[b];
-    const int L1 = 4 * L0;
-    const int L2 = base_len[b];
-    if (j >= L2) return;
-    const float r0 = r0s[b];
-    const float* x = lat + (long)(lat_row ? lat_row[b] : b) * lat_bstride + c;   // x[k] = x[k*C]
-    int i0, i1;
-    float lam2;
-    lin_src(r2, j, L1, i0, i1, lam2);
-    if (L2 == L1) {   // L0 <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
-        i0 = i1 = j;
-        lam2 = 0.f;
-    }
-    float y[2];
-    const int idx[2] = {i0, i1};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        int s[2];
-        float lam1;
-        lin_src(r1, idx[u], L0, s[0], s[1], lam1);
-        float w[2];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            int k0, k1;
-            float lam0;
-            stretch_src(r0, s[v], n, L0, k0, k1, lam0);
-            w[v] = lerp_f(x[(long)k0 * C], x[(long)k1 * C], lam0);
-        }
-        y[u] = lerp_f(w[0], w[1], lam1);
-    }
-    z[(long)b * z_bstride + (long)c * z_stride + j] = lerp_f(y[0], y[1], lam2);
+    interp_body<true, false>(lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len, z, z_stride, z_bstride, C, r1, r2);
 }
-
-// The interleaved-halves form, as interp2_h_kernel: a thread = eight channels of one position, one 16-byte store.
 __global__ __launch_bounds__(256) void interp3_h_kernel(const float* __restrict__ lat, long lat_bstride, const int* __restrict__ lat_row,
                                                         const int* __restrict__ n_lat, const int* __restrict__ l0s,
                                                         const float* __restrict__ r0s, const int* __restrict__ base_len,
                                                         _Float16* __restrict__ z, long z_stride, long z_bstride, int C, float r1, float r2) {
-    const int b = blockIdx.z;
-    const int c8 = blockIdx.y * 8;
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    const int n = n_lat[b];
-    const int L0 = l0s[b];
-    const int L1 = 4 * L0;
-    const int L2 = base_len[b];
-    if (j >= L2) return;
-    const float r0 = r0s[b];
-    const float* x = lat + (long)(lat_row ? lat_row[b] : b) * lat_bstride + c8;
-    int i0, i1;
-    float lam2;
-    lin_src(r2, j, L1, i0, i1, lam2);
-    if (L2 == L1) {   // L0 <= 2: an interpolation that keeps the length is a copy in torch, whatever the scale factor
-        i0 = i1 = j;
-        lam2 = 0.f;
-    }
-    const int idx[2] = {i0, i1};
-    float y[2][8];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        int s[2];
-        float lam1;
-        lin_src(r1, idx[u], L0, s[0], s[1], lam1);
-        float w[2][8];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            int k0, k1;
-            float lam0;
-            stretch_src(r0, s[v], n, L0, k0, k1, lam0);
-            const f32x4 a0 = *reinterpret_cast<const f32x4*>(x + (long)k0 * C), a1 = *reinterpret_cast<const f32x4*>(x + (long)k0 * C + 4);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(x + (long)k1 * C), b1 = *reinterpret_cast<const f32x4*>(x + (long)k1 * C + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                w[v][e] = lerp_f(a0[e], b0[e], lam0);
-                w[v][e + 4] = lerp_f(a1[e], b1[e], lam0);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) y[u][e] = lerp_f(w[0][e], w[1][e], lam1);
-    }
-    h16x8 o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (_Float16)lerp_f(y[0][e], y[1][e], lam2);
-    *reinterpret_cast<h16x8*>(z + (long)b * z_bstride + ((long)(c8 >> 4) * z_stride + j) * 16 + (c8 & 15)) = o;
+    interp_body<true, true>(lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len, z, z_stride, z_bstride, C, r1, r2);
+}
+
+// grid of either form (a thread per position; a channel, or eight, per blockIdx.y) and the two fixed scales; launch(grid, r1, r2)
+template <class Launch>
+static void launch_interp(const char* fp32_name, const char* half_name, int C, int B, int max_len, bool out_f16, Launch&& launch) {
+    trace_launch(out_f16 ? half_name : fp32_name);
+    launch(dim3((max_len + 255) / 256, out_f16 ? C / 8 : C, B), (float)(1.0 / (1024.0 / 256.0)), (float)(1.0 / (24000.0 / 22050.0)));
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_interp2(const float* lat, long lat_bstride, const int* lat_row, const int* n_lat, const int* base_len, float* z,
+                    long z_stride, long z_bstride, int C, int B, int max_len, hipStream_t st, bool out_f16) {
+    AUR_REQUIRE(!out_f16 || C % 16 == 0, "interp2: whole 16-channel chunks for the interleaved fp16 output");
+    launch_interp("interp2_kernel", "interp2_h_kernel", C, B, max_len, out_f16, [&](dim3 grid, float r1, float r2) {
+        if (out_f16)
+            hipLaunchKernelGGL(interp2_h_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, base_len,
+                               reinterpret_cast<_Float16*>(z), z_stride, z_bstride, C, r1, r2);
+        else
+            hipLaunchKernelGGL(interp2_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, base_len, z, z_stride, z_bstride, C,
+                               r1, r2);
+    });
 }
 
 void launch_interp3(const float* lat, long lat_bstride, const int* lat_row, const int* n_lat, const int* l0s, const float* r0s,
                     const int* base_len, float* z, long z_stride, long z_bstride, int C, int B, int max_len, hipStream_t st, bool out_f16) {
-    const float r1 = (float)(1.0 / (1024.0 / 256.0));
-    const float r2 = (float)(1.0 / (24000.0 / 22050.0));
-    if (out_f16) {
-        AUR_REQUIRE(C % 16 == 0, "interp3: whole 16-channel chunks for the interleaved fp16 output");
-        dim3 grid((max_len + 255) / 256, C / 8, B);
-        trace_launch("interp3_h_kernel");
-        hipLaunchKernelGGL(interp3_h_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len,
-                           reinterpret_cast<_Float16*>(z), z_stride, z_bstride, C, r1, r2);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    dim3 grid((max_len + 255) / 256, C, B);
-    trace_launch("interp3_kernel");
-    hipLaunchKernelGGL(interp3_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len, z, z_stride,
-                       z_bstride, C, r1, r2);
-    HIP_CHECK(hipGetLastError());
+    AUR_REQUIRE(!out_f16 || C % 16 == 0, "interp3: whole 16-channel chunks for the interleaved fp16 output");
+    launch_interp("interp3_kernel", "interp3_h_kernel", C, B, max_len, out_f16, [&](dim3 grid, float r1, float r2) {
+        if (out_f16)
+            hipLaunchKernelGGL(interp3_h_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len,
+                               reinterpret_cast<_Float16*>(z), z_stride, z_bstride, C, r1, r2);
+        else
+            hipLaunchKernelGGL(interp3_kernel, grid, dim3(256), 0, st, lat, lat_bstride, lat_row, n_lat, l0s, r0s, base_len, z, z_stride,
+                               z_bstride, C, r1, r2);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""GPU: every kernel the fp16 vocoder launches (run_vocoder with vocoder_fp16), one at a time, against the float64 reference of
+"""GPU: every kernel the fp16 vocoder launches (HifiGan::forward with vocoder_fp16), one at a time, against the float64 reference of
 tests/vocoder_ref.py on the fp16-rounded operands actually uploaded -- the LDS-DMA conv in its 8-wave all-halves form and its 4-wave
 transposed-conv form, the fused ResBlock round, interp2 and conv_post -- plus the fp32 conv kernel's conditioning and MRF modes.
 
