@@ -6,6 +6,7 @@ engine creation raises.  Nothing here imports oracle/.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 import weakref
@@ -44,13 +45,13 @@ class aur_seq_desc(C.Structure):
     _fields_ = [("text_ids", C.POINTER(C.c_int32)), ("n_text", C.c_int32), ("speaker_key", C.c_uint64),
                 ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32),
                 ("repetition_penalty", C.c_float), ("max_tokens", C.c_int32), ("seed", C.c_uint32),
-                ("ignore_stop", C.c_int32), ("priority", C.c_int32), ("speed", C.c_float)]
+                ("ignore_stop", C.c_int32), ("priority", C.c_int32), ("sample_rate", C.c_int32), ("speed", C.c_float)]
 
 
 class aur_result(C.Structure):
     _fields_ = [("seq_id", C.c_uint64), ("n_tokens", C.c_int32), ("tokens", C.POINTER(C.c_int32)),
                 ("n_samples", C.c_int32), ("wav", C.POINTER(C.c_float)), ("n_latent_rows", C.c_int32),
-                ("latents", C.POINTER(C.c_float)), ("error", C.c_int32)]
+                ("latents", C.POINTER(C.c_float)), ("error", C.c_int32), ("sample_rate", C.c_int32)]
 
 
 class aur_stats(C.Structure):
@@ -89,9 +90,9 @@ EXPORTS = [
     "aur_set_conditioning", "aur_set_conditioning_device", "aur_has_conditioning", "aur_compute_conditioning", "aur_comm_unique_id", "aur_comm_init", "aur_broadcast_conditioning",
     "aur_comm_info", "aur_conditioning_checksum",
     "aur_submit", "aur_step", "aur_poll_finished",
-    "aur_release", "aur_cancel", "aur_vocode", "aur_vocode_speed", "aur_sync", "aur_get_stats", "aur_get_load", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
+    "aur_release", "aur_cancel", "aur_vocode", "aur_vocode_speed", "aur_vocode_rate", "aur_sync", "aur_get_stats", "aur_get_load", "aur_reset_stats", "aur_set_profile", "aur_dbg_gemm", "aur_dbg_gemm_rows", "aur_dbg_gemm_rows_ksplit_stress", "aur_dbg_lane_xor_selftest",
     "aur_dbg_paged_attention", "aur_dbg_prompt_attention", "aur_dbg_layernorm", "aur_dbg_conv1d", "aur_dbg_conv1d_f16", "aur_dbg_prefill", "aur_dbg_sample",
-    "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_interp3", "aur_dbg_conv_post",
+    "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_interp3", "aur_dbg_conv_post", "aur_dbg_resample_out",
     "aur_dbg_gemm_tile", "aur_dbg_qkv_rows", "aur_dbg_rows_ln",
 ]
 
@@ -137,6 +138,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "aur_cancel": [eng, C.c_uint64],
         "aur_vocode": [eng, fp, ip, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_int64, ip],
         "aur_vocode_speed": [eng, fp, ip, fp, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_int64, ip],
+        "aur_vocode_rate": [eng, fp, ip, fp, ip, C.c_int32, C.c_int32, C.c_uint64, fp, C.c_int64, ip],
         "aur_sync": [eng],
         "aur_get_stats": [eng, C.POINTER(aur_stats)],
         "aur_get_load": [eng, C.POINTER(aur_load)],
@@ -164,6 +166,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "aur_dbg_interp2": [eng, fp, ip, ip] + [C.c_int32] * 6 + [fp, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_interp3": [eng, fp, ip, ip, fp] + [C.c_int32] * 6 + [fp, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_conv_post": [eng, fp, fp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, fp, C.c_float, C.POINTER(C.c_int64)],
+        "aur_dbg_resample_out": [eng, fp, ip, ip, C.c_int32, C.c_int32, fp, C.c_int32, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_prefill": [eng, ip, C.c_int32, C.c_uint64, C.c_float, fp, fp],
         "aur_dbg_sample": [eng, fp, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float,
                            C.POINTER(C.c_uint8), C.c_uint32, C.c_int32, ip],
@@ -187,6 +190,21 @@ def stretched_rows(n_lat: int, speed: float) -> int:
 def samples_for(n_lat: int, speed: float = 0.0) -> int:
     """Samples the vocoder makes of n_lat latent rows at `speed`: 256 * floor(4 L0' * 24000 / 22050)."""
     return 256 * int(np.floor(float(4 * stretched_rows(n_lat, speed)) * (24000.0 / 22050.0)))
+
+
+# output sample rates the engine delivers (aur_seq_desc.sample_rate; 0 = unset = 24000)
+OUTPUT_SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+RESAMPLE_TILE = 1024   # output samples one workgroup of resample_out_kernel owns (kResampleTile, csrc/vocoder_kernels.h)
+
+
+def samples_out(n: int, rate: int = 0) -> int:
+    """Samples that n samples at 24 kHz become at `rate` (0 = unset = 24000): ceil(n new / orig), 24000:rate reduced by their gcd --
+    the rule of csrc/vocoder_kernels.h, for sizing output buffers."""
+    rate = int(rate) or 24000
+    if rate not in OUTPUT_SAMPLE_RATES:
+        raise ValueError(f"sample rate {rate} is not one of {OUTPUT_SAMPLE_RATES}")
+    g = math.gcd(24000, rate)
+    return -(-int(n) * (rate // g) // (24000 // g))
 
 
 def _f32(a) -> np.ndarray:
@@ -240,6 +258,8 @@ class NativeEngine:
     """Thin object wrapper over the C ABI; one instance per GPU."""
     # poll(copy=False) hands out views of pinned host memory; past this many leased bytes (waveforms somebody keeps) new
     # results are copied instead, so that kept outputs cost pageable memory like the reference's, not pinned blocks
+    # (a result at an output rate of 48000 holds twice the pinned bytes of the same utterance at 24000, one at 8000 a third: the
+    # budget counts bytes, so fewer of the former stay leased)
     LEASE_BUDGET_BYTES = 2 << 30
 
     def __init__(self, n_layer: int = 30, max_seqs: int = 64, device: int = 0, max_prefill_rows: int = 0,
@@ -370,11 +390,12 @@ class NativeEngine:
     # -- sequences -------------------------------------------------------------------------------------
     def submit(self, text_ids: Sequence[int], speaker_key: int, temperature: float = 0.75, top_p: float = 0.85,
                top_k: int = 50, repetition_penalty: float = 5.0, max_tokens: int = 605, seed: int = 0,
-               ignore_stop: bool = False, priority: int = 0, speed: float = 0.0) -> int:
-        """`speed`: aur_seq_desc.speed, 0 = unset (= 1.0), else in [0.5, 2.0] (anything else: AurError, AUR_E_INVALID)."""
+               ignore_stop: bool = False, priority: int = 0, speed: float = 0.0, sample_rate: int = 0) -> int:
+        """`speed`: aur_seq_desc.speed, 0 = unset (= 1.0), else in [0.5, 2.0]; `sample_rate`: aur_seq_desc.sample_rate, 0 = unset
+        (= 24000), else one of OUTPUT_SAMPLE_RATES (anything else: AurError, AUR_E_INVALID)."""
         ids = _i32(list(text_ids))
         d = aur_seq_desc(_ip(ids), len(ids), speaker_key, temperature, top_p, top_k, repetition_penalty,
-                         max_tokens, seed & 0xFFFFFFFF, int(ignore_stop), int(priority), float(speed))
+                         max_tokens, seed & 0xFFFFFFFF, int(ignore_stop), int(priority), int(sample_rate), float(speed))
         sid = C.c_uint64()
         self._check(self.lib.aur_submit(self.h, C.byref(d), C.byref(sid)))
         return sid.value
@@ -415,6 +436,7 @@ class NativeEngine:
                 "wav": (arr(r.wav, (r.n_samples,)) if r.n_samples
                         else np.zeros(0, dtype=np.float32)),   # failed sequences carry no audio (error != 0)
                 "error": r.error,
+                "sample_rate": r.sample_rate,
             }
             if want_latents and r.n_latent_rows:
                 item["latents"] = arr(r.latents, (r.n_latent_rows, 1024))
@@ -461,8 +483,9 @@ class NativeEngine:
         return done
 
     def vocode(self, latents: np.ndarray, n_lat: Optional[Sequence[int]], speaker_key: int,
-               speed: Optional[Sequence[float]] = None) -> List[np.ndarray]:
-        """`speed` (optional, one per utterance, as aur_seq_desc.speed): aur_vocode_speed; None: aur_vocode."""
+               speed: Optional[Sequence[float]] = None, sample_rate: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+        """`speed` (optional, one per utterance, as aur_seq_desc.speed): aur_vocode_speed; None: aur_vocode.  `sample_rate` (optional,
+        one per utterance, as aur_seq_desc.sample_rate): aur_vocode_rate."""
         lat = _f32(latents)
         if lat.ndim == 2:
             lat = lat[None]
@@ -470,6 +493,18 @@ class NativeEngine:
         nl = _i32(n_lat if n_lat is not None else [t_max] * B)
         stride = int(np.floor(np.floor(t_max * 4.0) * (24000 / 22050))) * 256
         ns = np.zeros(B, dtype=np.int32)
+        if sample_rate is not None:
+            sp = None if speed is None else _f32(np.asarray(speed).reshape(B))
+            sr = _i32(np.asarray(sample_rate).reshape(B))
+            try:   # (what the engine refuses gets any stride)
+                stride = max([stride] + [samples_out(samples_for(int(n), 0.0 if sp is None else float(sp[b])), int(sr[b]))
+                                         for b, n in enumerate(nl)])
+            except (ValueError, OverflowError):
+                pass
+            wav = np.zeros((B, stride), dtype=np.float32)
+            self._check(self.lib.aur_vocode_rate(self.h, _fp(lat), _ip(nl), _fp(sp), _ip(sr), B, t_max, speaker_key, _fp(wav), stride,
+                                                 _ip(ns)))
+            return [wav[b, : ns[b]].copy() for b in range(B)]
         if speed is None:
             wav = np.zeros((B, stride), dtype=np.float32)
             self._check(self.lib.aur_vocode(self.h, _fp(lat), _ip(nl), B, t_max, speaker_key, _fp(wav), stride, _ip(ns)))
@@ -708,6 +743,18 @@ class NativeEngine:
         self._check(self.lib.aur_dbg_conv_post(self.h, _fp(x), _fp(w), _ip(lens), B, cin, L, slope, int(bool(x_f16_act)), _fp(wav), sentinel,
                                                C.byref(bad)))
         return wav, int(bad.value)
+
+    def dbg_resample_out(self, x, lens, rate, sentinel=-777.0):
+        """The output-rate resampler alone on x [B][L] (L = max(lens)), rate [B] as aur_seq_desc.sample_rate.  Returns
+        (out [B][max samples_out(lens[b], rate[b])], guard words changed)."""
+        x, lens, rate = _f32(x), _i32(lens), _i32(rate)
+        B, L = x.shape
+        assert lens.shape == rate.shape == (B,)
+        lout = max(samples_out(int(n), int(r)) for n, r in zip(lens, rate))
+        out = np.full((B, lout), sentinel, dtype=np.float32)
+        bad = C.c_int64(-1)
+        self._check(self.lib.aur_dbg_resample_out(self.h, _fp(x), _ip(lens), _ip(rate), B, L, _fp(out), lout, sentinel, C.byref(bad)))
+        return out, int(bad.value)
 
     def dbg_prefill(self, text_ids, speaker_key: int, repetition_penalty: float = 1.0):
         ids = _i32(list(text_ids))

@@ -1,7 +1,8 @@
 """TTSRequest — same fields, defaults and meaning as the reference dataclass
 (src/auralis/common/definitions/requests.py:134-277).  Fields the reference carries but never consumes on the
 synthesis path (do_sample, length_penalty, sound_norm_refs, load_sample_rate) are kept for
-drop-in compatibility.  `seed` is new surface (per-request noise stream; the reference has none); so are `priority` and `speed`."""
+drop-in compatibility.  `seed` is new surface (per-request noise stream; the reference has none); so are `priority`, `speed` and
+`output_sample_rate`."""
 from __future__ import annotations
 
 import copy as _copy
@@ -11,6 +12,9 @@ from dataclasses import dataclass, field
 from typing import AsyncGenerator, Callable, List, Optional, Union
 
 from .lang import get_language, validate_language
+
+# the rates the engine delivers (aur_seq_desc.sample_rate; include/auralis_amd.h)
+OUTPUT_SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
 
 
 @dataclass
@@ -56,8 +60,15 @@ class TTSRequest:
     # inference(speed=) rule), so pitch and loudness stay and nothing runs on the finished waveform (the reference's only speed
     # control is TTSOutput.change_speed, a phase vocoder over the audio)
     speed: float = 1.0
+    # new surface, like `speed`: the sample rate of the audio the request yields, one of OUTPUT_SAMPLE_RATES, handed to the engine as
+    # aur_seq_desc.sample_rate for every chunk -- the GPU resamples behind the vocoder (torchaudio's windowed sinc, the rule of the
+    # reference's TTSOutput.resample) and stores the result where the 24 kHz waveform would have gone; nothing runs on the host
+    output_sample_rate: int = 24000
 
     def __post_init__(self):
+        if isinstance(self.output_sample_rate, bool) or not isinstance(self.output_sample_rate, int) \
+                or self.output_sample_rate not in OUTPUT_SAMPLE_RATES:
+            raise ValueError(f"output_sample_rate must be one of {OUTPUT_SAMPLE_RATES}, got {self.output_sample_rate!r}")
         try:
             ok = math.isfinite(self.speed) and 0.5 <= float(self.speed) <= 2.0
         except TypeError:

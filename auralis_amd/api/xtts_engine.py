@@ -317,7 +317,10 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
                        # a latency-critical request: its first chunk is the one somebody waits for
                        **({"priority": int(request.priority)} if idx == 0 and getattr(request, "priority", 0) > 0 else {}),
                        # the speaking rate belongs to the whole request: every chunk carries it
-                       **({"speed": float(request.speed)} if getattr(request, "speed", 1.0) != 1.0 else {}))
+                       **({"speed": float(request.speed)} if getattr(request, "speed", 1.0) != 1.0 else {}),
+                       # so does the output rate; 24000 leaves the keyword out (engines and test doubles without it keep working)
+                       **({"sample_rate": int(request.output_sample_rate)}
+                          if getattr(request, "output_sample_rate", 24000) != 24000 else {}))
             if self._placer is None:
                 fut = self.driver.submit(loop, reregister=lambda: self.native.set_conditioning(key, g_np, s_np), **seq)
             else:
@@ -403,7 +406,7 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
         item = await generator.future
         # item["wav"] is the engine's own pinned result block (EngineDriver polls with copy=False): the TTSOutput's array is a view
         # of it and gives the block back when it is dropped (ResultLease); nothing is copied between the GPU's store and the caller
-        yield TTSOutput(array=item["wav"], sample_rate=24000,
+        yield TTSOutput(array=item["wav"], sample_rate=int(item.get("sample_rate", 24000)),
                         start_time=request.start_time if request is not None else None,
                         token_length=int(len(item["tokens"])))
 

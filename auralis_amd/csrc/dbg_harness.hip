@@ -1,5 +1,5 @@
 // Kernel test harness: the aur_dbg_* entry points of include/auralis_amd.h that run ONE kernel on host arrays (tests/test_gpu_kernels.py,
-// test_gpu_prefill_kernels.py, test_gpu_vocoder_kernels.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
+// test_gpu_prefill_kernels.py, test_gpu_vocoder_kernels.py, test_gpu_resample.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
 // the K-split scratch (DbgCtx) and nothing else, and the host rules of a launch from where the engine takes them: gpt_host.h (the decode
 // GEMMs' operands) and voc_net.h (the storage of a vocoder conv's tensors); aur_dbg_prefill and aur_dbg_sample drive real engine state
 // and live in engine.hip.
@@ -784,6 +784,40 @@ int aur_dbg_conv_post(aur_engine* e, const float* x, const float* w, const int32
         launch_conv_post(dx.as<float>(), dw.as<float>(), reinterpret_cast<float*>(gw.data()), dl.as<int>(), 1, Cin, L, (long)Cin * L, L, slope,
                          B, L, c.st, x_f16_act != 0);
         *guard_changed = gw.download(wav, c.st);
+    });
+}
+int aur_dbg_resample_out(aur_engine* e, const float* x, const int32_t* lens, const int32_t* rate, int32_t B, int32_t L, float* out,
+                         int32_t Lout, float guard_value, int64_t* guard_changed) {
+    CHECK_PTR(e);
+    CHECK_PTR(x);
+    CHECK_PTR(lens);
+    CHECK_PTR(rate);
+    CHECK_PTR(out);
+    CHECK_PTR(guard_changed);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        check_lens(lens, B, L, "dbg_resample_out: 1 <= lens[b] <= L = max(lens)");
+        std::vector<int> cls(B), n_out(B);
+        for (int b = 0; b < B; ++b) {
+            cls[b] = rate_class(rate[b]);
+            AUR_REQUIRE(cls[b] >= 0, "dbg_resample_out: rate 0 (unset) or one of 8000, 16000, 22050, 24000, 32000, 44100, 48000");
+            n_out[b] = (int)resampled_len(lens[b], cls[b]);
+        }
+        check_lens(n_out.data(), B, Lout, "dbg_resample_out: Lout = the longest output");
+        // the kernel stages with 16-byte loads: rows of whole float4s on the device, as the engine's staging buffer has them
+        const long Ld = (L + 3) & ~3L;
+        std::vector<float> xd((size_t)B * Ld, 0.f);
+        for (int b = 0; b < B; ++b) std::copy(x + (size_t)b * L, x + (size_t)(b + 1) * L, xd.begin() + (size_t)b * Ld);
+        DevBuf dx, dl, dc, dt;
+        GuardedBuf go;
+        dx.upload(xd);
+        dl.upload(lens, (size_t)B * 4);
+        dc.upload(cls);
+        dt.upload(resample_table());
+        go.upload(out, B, 1, Lout, false, guard_value);
+        launch_resample_out(dx.as<float>(), Ld, dl.as<int>(), 1, dc.as<int>(), dt.as<int>(), reinterpret_cast<float*>(go.data()), Lout, B, Lout,
+                            c.st);
+        *guard_changed = go.download(out, c.st);
     });
 }
 

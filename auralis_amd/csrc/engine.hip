@@ -530,6 +530,7 @@ public:
         AUR_REQUIRE(n_prompt <= cfg_.max_prefill_rows, "prompt longer than max_prefill_rows");
         AUR_REQUIRE(d.repetition_penalty > 0.f, "repetition_penalty > 0");
         AUR_REQUIRE(speed_valid(d.speed), "speed is 0 (unset) or in [0.5, 2.0]");
+        AUR_REQUIRE(rate_class(d.sample_rate) >= 0, "sample_rate is 0 (unset) or one of 8000, 16000, 22050, 24000, 32000, 44100, 48000");
         std::lock_guard<std::mutex> lk(mu_);
         {   // reject bad text ids / positions here, not in the middle of a batched prefill
             auto te = w_.find("text_emb"), tp = w_.find("text_pos");
@@ -575,6 +576,7 @@ public:
             r.n_latent_rows = s->n_latent_rows;
             r.latents = s->latents;
             r.error = s->error;
+            r.sample_rate = s->params.sample_rate ? s->params.sample_rate : 24000;
         }
         return n;
     }
@@ -852,8 +854,8 @@ public:
     }
 
     // ------------------------------------------------------------------ standalone vocoder
-    void vocode_host(const float* latents, const int* n_lat, const float* speed, int B, int t_max, uint64_t key, float* wav_out,
-                     int64_t wav_stride, int* n_samples_out) {
+    void vocode_host(const float* latents, const int* n_lat, const float* speed, const int* sample_rate, int B, int t_max, uint64_t key,
+                     float* wav_out, int64_t wav_stride, int* n_samples_out) {
         use();
         voc_->bind();
         const int row = speaker_row(key, false);
@@ -863,24 +865,28 @@ public:
         std::vector<int> nl(n_lat, n_lat + B), cond(B, row);
         std::vector<float> sp(B, 0.f);
         if (speed) sp.assign(speed, speed + B);
+        std::vector<int> sr(B, 0);
+        if (sample_rate) sr.assign(sample_rate, sample_rate + B);
         int max_samples = 0;
         for (int b = 0; b < B; ++b) {
             AUR_REQUIRE(nl[b] >= 1 && nl[b] <= t_max, "n_lat in [1,t_max]");
             AUR_REQUIRE(speed_valid(sp[b]), "speed is 0 (unset) or in [0.5, 2.0]");
-            max_samples = std::max(max_samples, frames_for(stretched_rows(nl[b], sp[b])) * 256);
+            AUR_REQUIRE(rate_class(sr[b]) >= 0, "sample_rate is 0 (unset) or one of 8000, 16000, 22050, 24000, 32000, 44100, 48000");
+            max_samples = std::max(max_samples, out_samples(nl[b], sp[b], sr[b]));
         }
         AUR_REQUIRE(wav_stride >= max_samples, "wav_stride too small");
+        max_samples = (max_samples + 3) & ~3;   // the device rows: whole 16-byte stores (voc_launch)
         tmp_lat_.ensure((size_t)B * t_max * kHidden * sizeof(float));
         HIP_CHECK(hipMemcpyAsync(tmp_lat_.p, latents, (size_t)B * t_max * kHidden * sizeof(float),
                                  hipMemcpyHostToDevice, st_voc_));
         tmp_wav_.ensure((size_t)B * max_samples * sizeof(float));
-        voc_->forward(B, nl, sp, tmp_lat_.as<float>(), (long)t_max * kHidden, nullptr, cond, tmp_wav_.as<float>(), max_samples,
+        voc_->forward(B, nl, sp, sr, tmp_lat_.as<float>(), (long)t_max * kHidden, nullptr, cond, tmp_wav_.as<float>(), max_samples,
                       voc_cond_.as<float>(), cfg_.profile != 0);
         stats_.vocoder_batches++;
         HIP_CHECK(hipStreamSynchronize(st_voc_));
         voc_->collect(stats_);
         for (int b = 0; b < B; ++b) {
-            const int ns = frames_for(stretched_rows(nl[b], sp[b])) * 256;
+            const int ns = out_samples(nl[b], sp[b], sr[b]);
             HIP_CHECK(hipMemcpy(wav_out + (long)b * wav_stride, tmp_wav_.as<float>() + (long)b * max_samples,
                                 (size_t)ns * sizeof(float), hipMemcpyDeviceToHost));
             if (n_samples_out) n_samples_out[b] = ns;
@@ -1666,11 +1672,16 @@ private:
         voc_queue_.erase(voc_queue_.begin(), voc_queue_.begin() + B);
         voc_nl_.resize(B);
         voc_speed_.resize(B);
+        voc_rate_.resize(B);
         std::vector<int> rows(B), cond(B);
-        voc_max_samples_ = maxT * 256;
+        // The result block's row stride: the longest utterance as it leaves, max_b n_out(b), in whole 16-byte stores.  At 24000 that is
+        // maxT * 256 as ever; a pass at 48000 pins up to twice those bytes (aur_seq_desc.sample_rate), one at 8000 a third.
+        voc_max_samples_ = 0;
         for (int b = 0; b < B; ++b) {
             voc_nl_[b] = (int)voc_batch_[b]->tokens.size();
             voc_speed_[b] = voc_batch_[b]->params.speed;
+            voc_rate_[b] = voc_batch_[b]->params.sample_rate;
+            voc_max_samples_ = std::max(voc_max_samples_, (out_samples(voc_nl_[b], voc_speed_[b], voc_rate_[b]) + 3) & ~3);
             rows[b] = voc_batch_[b]->pool_idx;
             cond[b] = voc_batch_[b]->spk_row;
         }
@@ -1696,7 +1707,7 @@ private:
         // decode step being over).  hipHostMalloc memory is device-visible and coherent; the event below orders the host's reads.
         float* hw = voc_block_->buf.as<float>();
         float* hl = hw + (size_t)B * voc_max_samples_;
-        voc_->forward(B, voc_nl_, voc_speed_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_,
+        voc_->forward(B, voc_nl_, voc_speed_, voc_rate_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_,
                       voc_cond_.as<float>(), cfg_.profile != 0);
         stats_.vocoder_batches++;
         for (int b = 0; b < B && cfg_.return_latents; ++b)
@@ -1722,7 +1733,7 @@ private:
         const float* hl = hw + (size_t)B * voc_max_samples_;
         for (int b = 0; b < B; ++b) {
             Seq* s = voc_batch_[b];
-            const int ns = frames_for(stretched_rows(voc_nl_[b], voc_speed_[b])) * 256;
+            const int ns = out_samples(voc_nl_[b], voc_speed_[b], voc_rate_[b]);   // delivered samples, at the sequence's rate
             s->wav = hw + (size_t)b * voc_max_samples_;
             s->n_samples = ns;
             if (cfg_.return_latents) {
@@ -1804,6 +1815,7 @@ private:
     std::vector<Seq*> voc_batch_;
     std::vector<int> voc_nl_;
     std::vector<float> voc_speed_;      // aur_seq_desc.speed of the batch's sequences
+    std::vector<int> voc_rate_;         // aur_seq_desc.sample_rate of the batch's sequences
     bool voc_split_rest_ = false;       // the last pass left part of the queue behind because of the workspace bound
     int voc_max_samples_ = 0;
     bool voc_active_ = false;
@@ -1983,11 +1995,15 @@ int aur_vocode(aur_engine* e, const float* latents, const int32_t* n_lat, int32_
 }
 int aur_vocode_speed(aur_engine* e, const float* latents, const int32_t* n_lat, const float* speed, int32_t B, int32_t t_max,
                      uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out) {
+    return aur_vocode_rate(e, latents, n_lat, speed, nullptr, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out);
+}
+int aur_vocode_rate(aur_engine* e, const float* latents, const int32_t* n_lat, const float* speed, const int32_t* sample_rate, int32_t B,
+                    int32_t t_max, uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out) {
     CHECK_PTR(e);
     CHECK_PTR(latents);
     CHECK_PTR(n_lat);
     CHECK_PTR(wav_out);
-    return bound(e, [&] { e->impl.vocode_host(latents, n_lat, speed, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out); });
+    return bound(e, [&] { e->impl.vocode_host(latents, n_lat, speed, sample_rate, B, t_max, speaker_key, wav_out, wav_stride, n_samples_out); });
 }
 int aur_sync(aur_engine* e) {
     CHECK_PTR(e);

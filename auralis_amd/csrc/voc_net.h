@@ -89,10 +89,16 @@ inline void round_cost(ProfEvent& e, const RoundArgs& a, int KS, double totT) {
     e.kind = a.C == 64 ? 2 : 3; e.flops = 2.0 * (2.0 * a.C * KS * a.C * tot) /* conv1 + conv2 */; e.bytes = a.C * tot * (2.0 + io);
 }
 
+// samples utterance b of a pass leaves: the vocoder's 256 per frame at 24 kHz, then the output rate (0 = unset = 24000)
+inline int out_samples(int n_lat, float speed, int sample_rate) {
+    return (int)resampled_len((long)frames_for(stretched_rows(n_lat, speed)) * 256, rate_class(sample_rate));
+}
+
 class HifiGan {
 public:
     using WeightFn = std::function<const float*(const std::string&)>;
-    HifiGan(WeightFn w, hipStream_t st, VocLayout lay) : W_(std::move(w)), st_(st), lay_(lay) {}
+    // (on the engine's device: the resampler's table, no weight of the checkpoint, goes up here)
+    HifiGan(WeightFn w, hipStream_t st, VocLayout lay) : W_(std::move(w)), st_(st), lay_(lay) { v_rtab_.upload(resample_table()); }
     ~HifiGan() {   // (not copyable: the workspace buffers are not)
         for (auto& e : events_) (void)hipEventDestroy(e.a), (void)hipEventDestroy(e.b);
     }
@@ -118,16 +124,19 @@ public:
     void unbind() { bound_ = false; }
 
     // latents: d_lat + lat_row[b]*lat_bstride (lat_row nullable => b); wav: d_wav + b*wav_bstride; speed[b] as aur_seq_desc.speed;
+    // rate[b] as aur_seq_desc.sample_rate (a supported rate or 0), utterance b leaves out_samples(n_lat[b], speed[b], rate[b]) samples;
     // condt: the conditioning table, row cond_row[b] of kCondStride floats.  profile: every conv launch between an event pair (collect)
-    void forward(int B, const std::vector<int>& n_lat, const std::vector<float>& speed, const float* d_lat, long lat_bstride,
-                 const std::vector<int>* lat_row, const std::vector<int>& cond_row, float* d_wav, long wav_bstride, const float* condt,
-                 bool profile) {
+    void forward(int B, const std::vector<int>& n_lat, const std::vector<float>& speed, const std::vector<int>& rate, const float* d_lat,
+                 long lat_bstride, const std::vector<int>* lat_row, const std::vector<int>& cond_row, float* d_wav, long wav_bstride,
+                 const float* condt, bool profile) {
         bind();
         profile_ = profile;
-        meta_.assign(6 * (size_t)B, 0);
+        meta_.assign(7 * (size_t)B, 0);
         int maxT = 0;
         double totT = 0;   // frames of the batch
         bool stretched = false;   // some utterance's speed changes its row count: the three-stage kernel
+        bool resampled = false;   // some utterance leaves at another rate than the vocoder's 24000: conv_post stages, resample_out_kernel
+        long max_out = 0;         // stores
         for (int b = 0; b < B; ++b) {
             const int l0 = stretched_rows(n_lat[b], speed[b]);
             const float r0 = stretch_ratio(speed[b]);
@@ -137,7 +146,11 @@ public:
             meta_[3 * B + b] = lat_row ? (*lat_row)[b] : b;
             meta_[4 * B + b] = l0;
             std::memcpy(&meta_[5 * B + b], &r0, 4);
+            meta_[6 * B + b] = rate_class(rate[b]);
+            AUR_REQUIRE(meta_[6 * B + b] >= 0, "sample_rate is 0 (unset) or one of 8000, 16000, 22050, 24000, 32000, 44100, 48000");
             stretched |= l0 != n_lat[b];
+            resampled |= meta_[6 * B + b] != 0;
+            max_out = std::max(max_out, resampled_len((long)meta_[B + b] * 256, meta_[6 * B + b]));
             maxT = std::max(maxT, meta_[B + b]);
             totT += meta_[B + b];
         }
@@ -208,8 +221,17 @@ public:
                     conv(VocRole::C2, i, l2, Bb, mode ? E : S1, -1, KS, 1, mode, mode ? mean_slope : 0.1f, r, mode ? D : nullptr);
                 }
         }
-        launch_conv_post(static_cast<const float*>(E), post_, d_wav, d_len, 256, 32, (long)T * 256, (long)32 * T * 256, wav_bstride, 0.01f, B,
-                         maxT * 256, st_, h);
+        // (a batch in which every utterance leaves at 24000 is what it was: conv_post stores into d_wav, same launches, same arguments)
+        float* post_out = d_wav;
+        long post_bstride = wav_bstride;
+        if (resampled) {   // conv_post stores into a device staging buffer [B][maxT * 256], allocated on the first such pass
+            v_wav_.ensure(Bz * T * 256 * 4);
+            post_out = v_wav_.as<float>(), post_bstride = (long)T * 256;
+        }
+        launch_conv_post(static_cast<const float*>(E), post_, post_out, d_len, 256, 32, (long)T * 256, (long)32 * T * 256, post_bstride, 0.01f,
+                         B, maxT * 256, st_, h);
+        if (resampled)
+            launch_resample_out(post_out, post_bstride, d_len, 256, d_nlat + 6 * B, v_rtab_.as<int>(), d_wav, wav_bstride, B, max_out, st_);
         HIP_CHECK(hipEventRecord(events_[whole].b, st_));
     }
 
@@ -251,6 +273,7 @@ private:
     ConvLayer pre_, ups_[4], c1_[4][3][3], c2_[4][3][3];
     const float* post_ = nullptr;
     DevBuf v_meta_, v_z_, v_s0_, v_S0_, v_S1_, v_S2_, v_B_, v_D_, v_E_, v_zero_;
+    DevBuf v_wav_, v_rtab_;   // output rates other than 24000: conv_post's staging buffer, resample_table() on the device
     std::vector<int> meta_;   // host copy of v_meta_ (member: the async H2D copy must not outlive its source)
     std::vector<ProfEvent> events_;   // of the forward in flight: the pair around all of it, then one per profiled launch
     size_t n_events_ = 0;

@@ -2,6 +2,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "common.h"
 
@@ -120,6 +121,40 @@ void launch_interp3(const float* lat, long lat_bstride, const int* lat_row, cons
 void launch_conv_post(const float* x, const float* w, float* wav, const int* base_len, int len_mul, int Cin,
                       long x_stride, long x_bstride, long wav_bstride, float slope, int B, int max_len,
                       hipStream_t st, bool x_f16_act = false);   // x_f16_act: x = fp16(lrelu(.)) already, interleaved halves
+
+// Output sample rate (aur_seq_desc.sample_rate; 0 = unset = 24000): the finished 24 kHz waveform is resampled on the GPU by the
+// Hann-windowed sinc of torchaudio.functional.resample (lowpass_filter_width 6, rolloff 0.99), the rule auralis_amd/conditioning.py
+// restates.  For 24000:new reduced by their gcd to orig:new, base = min(orig, new) * 0.99, width = ceil(6 orig / base),
+//   c[p][k] = sinc(pi t) cos^2(pi t / 12) base / orig,  t = clamp((-p / new + (k - width) / orig) base, -6, 6),  k in [0, 2 width + orig)
+//   y[j new + p] = sum_k c[p][k] xpad[j orig + k]       xpad = the waveform behind `width` zeros, zeros after its last sample
+// and an utterance of n samples yields ceil(n new / orig).  One definition for the kernel, the host's sizing and the tests.
+// Rate classes: 0 = 24000 (copied), then the six resampled rates.
+constexpr int kOutRates[7] = {24000, 8000, 16000, 22050, 32000, 44100, 48000};
+constexpr int kResampleTile = 1024;   // output samples a workgroup of resample_out_kernel owns, counted from the utterance's first
+inline int rate_class(int sample_rate) {   // -1: not a supported rate
+    if (sample_rate == 0) return 0;
+    for (int c = 0; c < 7; ++c)
+        if (kOutRates[c] == sample_rate) return c;
+    return -1;
+}
+inline int resample_gcd(int cls) { return cls == 3 ? 150 : cls == 5 ? 300 : cls == 0 ? 24000 : 8000; }
+// samples of an utterance of n 24 kHz samples in rate class cls: ceil(n new / orig)
+inline long resampled_len(long n, int cls) {
+    const long g = resample_gcd(cls), orig = 24000 / g, nw = kOutRates[cls] / g;
+    return (n * nw + orig - 1) / orig;
+}
+// The device table of resample_out_kernel as 32-bit words (coefficients as float bits): seven headers of 8 words
+// {orig, new, taps, width, first, coef, 0, 0}, then per class the first dense tap k of every phase (word `first` on) and the kept
+// coefficients [taps][new] (word `coef` on).  Built in double and rounded once to fp32; taps in the clamped region |t| = 6 are zero
+// in fp32 and dropped: every phase keeps one run of `taps` dense taps (13 at 32 k / 44.1 k / 48 k, 14 at 22.05 k, 19 at 16 k, 37 at
+// 8 k), about 20 KB for the six classes.
+const std::vector<int>& resample_table();
+// out[b][m] for m < resampled_len(base_len[b] * len_mul, cls[b]), one fp32 fma chain per sample in ascending tap order; cls[b] == 0
+// copies.  x [B][x_bstride], x_bstride a multiple of 4 that holds the longest utterance rounded up to 4 (16-byte loads; what a row holds
+// past its utterance is never used: positions outside [0, n_b) are zeros by the length).  tab: resample_table() on the device.
+// max_out: the longest output (grid sizing).
+void launch_resample_out(const float* x, long x_bstride, const int* base_len, int len_mul, const int* cls, const int* tab, float* out,
+                         long o_bstride, int B, long max_out, hipStream_t st);
 
 // y[b][r] = bias[r] + sum_k W[r][k] * g[b][k]      (1x1 conditioning convs on the speaker embedding)
 void launch_gemv_rows(const float* W, const float* bias, const float* g, float* y, int R, int K, int B,

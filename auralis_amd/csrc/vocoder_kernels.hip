@@ -13,6 +13,8 @@
 // 4 LDS dword reads.  D layout: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 #include "vocoder_kernels.h"
 
+#include <cstdint>
+#include <cstring>
 #include <type_traits>
 
 namespace aur {
@@ -1339,6 +1341,142 @@ void launch_conv_post(const float* x, const float* w, float* wav, const int* bas
     else
         hipLaunchKernelGGL(conv_post_kernel<false>, grid, dim3(256), 0, st, x, w, wav, base_len, len_mul, Cin, x_stride,
                            x_bstride, wav_bstride, slope);
+    HIP_CHECK(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
+// Output sample rate (vocoder_kernels.h): the windowed-sinc resampler behind conv_post, one launch per vocoder pass, grid = (output
+// tiles, B), ragged.  A workgroup owns kResampleTile output samples counted from the utterance's first, stages the input span they
+// read (tap halo included) and its class's coefficients in LDS, and every lane accumulates four outputs, each as ONE fp32 fma chain
+// in ascending tap order: a sample's bits depend on its index and the utterance alone, not on batch, tile or neighbour.
+// LDS reads of the chain, lane l on output m0 + l (+ 256 i), 32 banks per 32-lane half: 8 k reads x at stride 3, conflict-free
+// (3 is odd).  16 k reads 3 (l / 2) + first[l % 2], two stride-3 runs of 16 lanes that lie first[1] - first[0] = 2 apart: lanes 2 j and
+// 2 (j + 10) + 1 meet on a bank, six banks of a half are read twice.  32 k, 44.1 k (147:80) and 48 k advance by less than one input
+// per output: neighbouring lanes share an address (a broadcast) or step by one, no conflict.  22.05 k (147:160) steps by one and skips
+// an input every 11 or 12 lanes, 34 or 35 addresses for 32 lanes: two or three banks are read twice.  The coefficients lie
+// [tap][phase]: consecutive lanes, consecutive words (8 k: one word, a broadcast).
+constexpr int kRsXs = 3136;            // staged input floats: the 8 k class reads 3 * 1023 + 41 of them, plus the 16-byte alignment
+constexpr int kRsCoef = 147 * 14;      // the largest class table (22.05 k: 147 phases x 14 taps)
+__global__ __launch_bounds__(256) void resample_out_kernel(const float* __restrict__ x, long x_bstride, const int* __restrict__ base_len,
+                                                           int len_mul, const int* __restrict__ cls, const int* __restrict__ tab,
+                                                           float* __restrict__ out, long o_bstride) {
+    __shared__ __attribute__((aligned(16))) float xs[kRsXs];
+    __shared__ __attribute__((aligned(16))) float os[kResampleTile];
+    __shared__ float cs[kRsCoef];
+    __shared__ int fs[147];
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = base_len[b] * len_mul;
+    const int* hd = tab + 8 * cls[b];
+    const int orig = hd[0], nw = hd[1], taps = hd[2], width = hd[3];
+    const long n_out = ((long)n * nw + orig - 1) / orig;
+    const long m0 = (long)blockIdx.x * kResampleTile;
+    if (m0 >= n_out) return;
+    const float* xb = x + (long)b * x_bstride;
+    float* ob = out + (long)b * o_bstride;
+    const long m4 = m0 + 4 * tid;   // the four samples this lane stores
+    const bool vec_out = (o_bstride & 3) == 0 && m4 + 3 < n_out;
+    if (cls[b] == 0) {   // 24000 inside a mixed batch: copied bit for bit
+        if (m4 >= n_out) return;
+        if (vec_out) {
+            *reinterpret_cast<f32x4*>(ob + m4) = *reinterpret_cast<const f32x4*>(xb + m4);
+        } else {
+            for (int i = 0; i < 4 && m4 + i < n_out; ++i) ob[m4 + i] = xb[m4 + i];
+        }
+        return;
+    }
+    for (int i = tid; i < taps * nw; i += 256) cs[i] = __int_as_float(tab[hd[5] + i]);
+    for (int i = tid; i < nw; i += 256) fs[i] = tab[hd[4] + i];
+    // the span [lo4, hi) of x the tile's chains read: blocks j0 .. j1 of `orig` inputs, `width` zeros in front of the utterance
+    const long m_last = (m0 + kResampleTile < n_out ? m0 + kResampleTile : n_out) - 1;
+    const long j0 = m0 / nw, j1 = m_last / nw;
+    const long lo4 = (j0 * orig - width) & ~3L, hi = j1 * orig - width + 2 * width + orig;
+    const int n4 = (int)((hi - lo4 + 3) >> 2);
+    for (int v = tid; v < n4; v += 256) {
+        const long i = lo4 + 4 * v;
+        f32x4 q = {0.f, 0.f, 0.f, 0.f};
+        if (i >= 0 && i < n) {   // zero-filled by the length: what the row holds past n is an earlier batch's
+            q = *reinterpret_cast<const f32x4*>(xb + i);
+            if (i + 1 >= n) q.y = 0.f;
+            if (i + 2 >= n) q.z = 0.f;
+            if (i + 3 >= n) q.w = 0.f;
+        }
+        *reinterpret_cast<f32x4*>(&xs[4 * v]) = q;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long m = m0 + tid + 256 * i;
+        if (m < n_out) {
+            const long j = m / nw;
+            const int p = (int)(m - j * nw);
+            const float* xp = xs + (int)(j * orig - width - lo4) + fs[p];
+            const float* cp = cs + p;
+            float s = 0.f;
+            for (int t = 0; t < taps; ++t) s = fmaf(cp[t * nw], xp[t], s);
+            os[tid + 256 * i] = s;
+        }
+    }
+    __syncthreads();
+    if (m4 >= n_out) return;
+    if (vec_out) {
+        *reinterpret_cast<f32x4*>(ob + m4) = *reinterpret_cast<const f32x4*>(&os[4 * tid]);
+    } else {
+        for (int i = 0; i < 4 && m4 + i < n_out; ++i) ob[m4 + i] = os[4 * tid + i];
+    }
+}
+
+const std::vector<int>& resample_table() {
+    static const std::vector<int> image = [] {
+        std::vector<int> img(7 * 8, 0);
+        img[0] = img[1] = img[2] = 1;   // class 0: 1:1, one tap (the kernel copies)
+        for (int c = 1; c < 7; ++c) {
+            const int g = resample_gcd(c), orig = 24000 / g, nw = kOutRates[c] / g;
+            const double base = std::min(orig, nw) * 0.99, pi = 3.14159265358979323846;
+            const int width = (int)std::ceil(6.0 * orig / base), K = 2 * width + orig;
+            std::vector<float> dense((size_t)nw * K);
+            int taps = 1;
+            std::vector<int> first(nw);
+            for (int p = 0; p < nw; ++p) {
+                int lo = K, hi = -1;
+                for (int k = 0; k < K; ++k) {
+                    double t = ((double)-p / nw + (double)(k - width) / orig) * base;
+                    t = std::min(6.0, std::max(-6.0, t));
+                    const double wnd = std::cos(t * pi / 6.0 / 2.0), tt = t * pi;
+                    const float cf = (float)((tt == 0.0 ? 1.0 : std::sin(tt) / tt) * wnd * wnd * (base / orig));
+                    dense[(size_t)p * K + k] = cf;
+                    if (cf != 0.f) lo = std::min(lo, k), hi = k;
+                }
+                first[p] = lo;
+                taps = std::max(taps, hi - lo + 1);
+            }
+            const int first_off = (int)img.size();
+            for (int p = 0; p < nw; ++p) img.push_back(first[p] = std::min(first[p], K - taps));   // a shorter run: zeros in front
+            const int coef_off = (int)img.size();
+            for (int t = 0; t < taps; ++t)
+                for (int p = 0; p < nw; ++p) {
+                    int bits;
+                    std::memcpy(&bits, &dense[(size_t)p * K + first[p] + t], 4);
+                    img.push_back(bits);
+                }
+            const int hd[8] = {orig, nw, taps, width, first_off, coef_off, 0, 0};
+            std::copy(hd, hd + 8, img.begin() + 8 * c);
+            // what the kernel's LDS holds: a tile spans at most (new - 1 + tile - 1) / new blocks of orig inputs past its first
+            AUR_REQUIRE(taps * nw <= kRsCoef && nw <= 147, "resample table: class larger than the kernel's LDS tables");
+            AUR_REQUIRE((long)((nw - 1 + kResampleTile - 1) / nw) * orig + K + 6 <= kRsXs, "resample table: input span larger than the kernel's LDS");
+        }
+        return img;
+    }();
+    return image;
+}
+
+void launch_resample_out(const float* x, long x_bstride, const int* base_len, int len_mul, const int* cls, const int* tab, float* out,
+                         long o_bstride, int B, long max_out, hipStream_t st) {
+    AUR_REQUIRE(B >= 1 && max_out >= 1 && (x_bstride & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0,
+                "resample_out: 16-byte aligned rows");
+    dim3 grid((unsigned)((max_out + kResampleTile - 1) / kResampleTile), B);
+    trace_launch("resample_out_kernel");
+    hipLaunchKernelGGL(resample_out_kernel, grid, dim3(256), 0, st, x, x_bstride, base_len, len_mul, cls, tab, out, o_bstride);
     HIP_CHECK(hipGetLastError());
 }
 

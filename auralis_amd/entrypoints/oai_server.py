@@ -24,7 +24,7 @@ from fastapi import FastAPI, Header, HTTPException, Request
 from fastapi.responses import JSONResponse, Response, StreamingResponse
 from pydantic import BaseModel, Field, field_validator
 
-from ..api.requests import TTSRequest
+from ..api.requests import OUTPUT_SAMPLE_RATES, TTSRequest
 from ..api.tts import TTS
 
 _MEDIA = {"wav": "audio/wav", "pcm": "audio/pcm", "mp3": "audio/mpeg", "opus": "audio/opus", "aac": "audio/aac",
@@ -37,6 +37,7 @@ class AudioSpeechGenerationRequest(BaseModel):
     voice: List[str] = Field(..., description="List of base64-encoded reference files")
     response_format: Literal["mp3", "opus", "aac", "flac", "wav", "pcm"] = "wav"
     speed: float = 1.0
+    sample_rate: Optional[int] = None   # TTSRequest.output_sample_rate (new surface); None: the server's --sample-rate
     # TTSRequest parameters (defaults of requests.py:164-190)
     enhance_speech: bool = False
     language: str = "auto"
@@ -63,8 +64,10 @@ class AudioSpeechGenerationRequest(BaseModel):
                 raise ValueError("Invalid base64 encoding in voice file")
         return v
 
-    def to_tts_request(self) -> TTSRequest:
+    def to_tts_request(self, sample_rate: int = 24000) -> TTSRequest:
+        """`sample_rate`: the rate a request without the field gets; an unsupported one raises ValueError (TTSRequest)"""
         return TTSRequest(text=self.input, stream=False, speaker_files=[base64.b64decode(f) for f in self.voice],
+                          output_sample_rate=sample_rate if self.sample_rate is None else self.sample_rate,
                           enhance_speech=self.enhance_speech, language=self.language,
                           max_ref_length=self.max_ref_length, gpt_cond_len=self.gpt_cond_len,
                           gpt_cond_chunk_len=self.gpt_cond_chunk_len, temperature=self.temperature, top_p=self.top_p,
@@ -78,7 +81,7 @@ class ChatCompletionMessage(BaseModel):
 
 
 _TTS_FIELDS = ("enhance_speech", "language", "max_ref_length", "gpt_cond_len", "gpt_cond_chunk_len", "temperature", "top_p",
-               "top_k", "repetition_penalty", "length_penalty", "do_sample")
+               "top_k", "repetition_penalty", "length_penalty", "do_sample", "sample_rate")
 
 
 class VoiceChatCompletionRequest(BaseModel):
@@ -102,6 +105,7 @@ class VoiceChatCompletionRequest(BaseModel):
     repetition_penalty: float = 5.0
     length_penalty: float = 1.0
     do_sample: bool = True
+    sample_rate: Optional[int] = None   # TTSRequest.output_sample_rate of the audio events; None: the server's --sample-rate
 
     @field_validator("openai_api_url")
     @classmethod
@@ -129,9 +133,10 @@ class VoiceChatCompletionRequest(BaseModel):
                 raise ValueError("Invalid base64 encoding in speaker file")
         return v
 
-    def to_tts_request(self, text: str = "") -> TTSRequest:
+    def to_tts_request(self, text: str = "", sample_rate: int = 24000) -> TTSRequest:
         return TTSRequest(text=text, stream=False, speaker_files=[base64.b64decode(f) for f in self.speaker_files],
-                          **{k: getattr(self, k) for k in _TTS_FIELDS})
+                          output_sample_rate=sample_rate if self.sample_rate is None else self.sample_rate,
+                          **{k: getattr(self, k) for k in _TTS_FIELDS if k != "sample_rate"})
 
     def to_openai_request(self) -> Dict[str, Any]:
         """What goes upstream: everything except the speech-side fields, always streamed (openai.py:99-108)."""
@@ -166,15 +171,19 @@ async def run_unless_disconnected(http_request: Any, awaitable, poll_s: float = 
             task.cancel()
 
 
-def create_app(tts: Optional[TTS], speed_mode: str = "stretch") -> FastAPI:
+def create_app(tts: Optional[TTS], speed_mode: str = "stretch", sample_rate: int = 24000) -> FastAPI:
     """`speed_mode`: what the OpenAI `speed` field of /v1/audio/speech does.  "stretch" (default, the reference's behaviour): the
     finished waveform goes through TTSOutput.change_speed, a phase vocoder on the host.  "latent": the value, clamped to [0.5, 2.0],
     becomes TTSRequest.speed -- the engine stretches the GPT latents ahead of the vocoder and nothing runs on the waveform."""
     if speed_mode not in ("stretch", "latent"):
         raise ValueError(f"speed_mode must be 'stretch' or 'latent', got {speed_mode!r}")
+    # `sample_rate`: the output rate of a request that names none (TTSRequest.output_sample_rate; the engine resamples on the GPU)
+    if sample_rate not in OUTPUT_SAMPLE_RATES:
+        raise ValueError(f"sample_rate must be one of {OUTPUT_SAMPLE_RATES}, got {sample_rate!r}")
     app = FastAPI(title="auralis_amd TTS server")
     app.state.tts = tts
     app.state.speed_mode = speed_mode
+    app.state.sample_rate = sample_rate
 
     @app.post("/v1/audio/speech")
     async def generate_audio(request: AudioSpeechGenerationRequest, http_request: Request):
@@ -183,7 +192,7 @@ def create_app(tts: Optional[TTS], speed_mode: str = "stretch") -> FastAPI:
             raise HTTPException(status_code=500, detail="TTS engine not initialized")
         try:
             # the facade owns its own event loop thread: hop over to it and await the result here
-            tts_request = request.to_tts_request()
+            tts_request = request.to_tts_request(sample_rate)   # (an unsupported rate: ValueError, the envelope below)
             if speed_mode == "latent":
                 tts_request.speed = min(2.0, max(0.5, float(request.speed)))
             fut = asyncio.run_coroutine_threadsafe(engine.generate_speech_async(tts_request), engine._loop)
@@ -220,7 +229,7 @@ def create_app(tts: Optional[TTS], speed_mode: str = "stretch") -> FastAPI:
             request_id = uuid.uuid4().hex
 
             async def audio_event(text: str) -> str:
-                req = request.to_tts_request(text=text)   # (language "auto" is resolved from this piece of text)
+                req = request.to_tts_request(text=text, sample_rate=sample_rate)   # (language "auto" is resolved from this piece of text)
                 out = await _speak(engine, req)
                 b64 = base64.b64encode(out.to_bytes()).decode("utf-8")
                 return f"data: {json.dumps({'id': request_id, 'object': 'audio.chunk', 'data': b64})}\n\n"
@@ -301,13 +310,15 @@ def main():
     p.add_argument("--speed-mode", choices=("stretch", "latent"), default="stretch",
                    help="the request's `speed`: stretch = phase vocoder over the finished waveform (the reference's behaviour); "
                         "latent = the engine stretches the GPT latents ahead of the vocoder (TTSRequest.speed, clamped to [0.5, 2.0])")
+    p.add_argument("--sample-rate", type=int, choices=OUTPUT_SAMPLE_RATES, default=24000,
+                   help="output sample rate of requests that name none (`sample_rate`); resampled on the GPU behind the vocoder")
     p.add_argument("--devices", type=_device_list, default=None, metavar="0,1,2,3",
                    help="comma-separated GPU indices: one engine per entry in this process, chunks placed on the least loaded one "
                         "(--max_concurrency is then slots PER ENGINE); default: one engine on device 0")
     a = p.parse_args()
     tts = TTS(scheduler_max_concurrency=a.max_concurrency).from_pretrained(a.model, gpt=a.gpt, kv=a.kv,
                                                                            **({"devices": a.devices} if a.devices is not None else {}))
-    uvicorn.run(create_app(tts, speed_mode=a.speed_mode), host=a.host, port=a.port)
+    uvicorn.run(create_app(tts, speed_mode=a.speed_mode, sample_rate=a.sample_rate), host=a.host, port=a.port)
 
 
 if __name__ == "__main__":

@@ -252,4 +252,8 @@ def synthesize_sharded(tts, requests: Sequence[TTSRequest], window: Optional[int
     parts = [pcm for _, pcm in stream_sharded(tts, requests, window, paragraphs_per_block, dst)]
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1 and dist.get_rank() != dst:
         return None
-    return TTSOutput(array=np.concatenate(parts) if parts else np.zeros(0, np.float32), sample_rate=24000)
+    # the parts are the requests' audio as the engine delivered it: at their output_sample_rate, which has to be one for one waveform
+    rates = {int(getattr(r, "output_sample_rate", 24000)) for r in requests} or {24000}
+    if len(rates) != 1:
+        raise ValueError(f"synthesize_sharded: one output_sample_rate for the whole text, got {sorted(rates)}")
+    return TTSOutput(array=np.concatenate(parts) if parts else np.zeros(0, np.float32), sample_rate=rates.pop())

@@ -115,6 +115,17 @@ typedef struct aur_seq_desc {
                                  vocoded as soon as its tokens are done, and while it waits or runs the engine admits normal
                                  sequences only up to aur_config.urgent_rows running ones (a decode step's time grows with its
                                  rows).  Results do not depend on it */
+    int32_t sample_rate;      /* output sample rate in Hz (new surface, like speed; the reference's counterpart is TTSOutput.resample,
+                                 torchaudio.functional.resample over the finished waveform on the host).  0 = unset = 24000, the vocoder's
+                                 own rate; otherwise one of 8000, 16000, 22050, 24000, 32000, 44100, 48000, anything else makes aur_submit
+                                 fail with AUR_E_INVALID.  The rule is torchaudio's Hann-windowed sinc, lowpass_filter_width 6, rolloff
+                                 0.99: for 24000:rate reduced by their gcd to orig:new, base = min(orig, new) * 0.99,
+                                 width = ceil(6 orig / base), c[p][k] = sinc(pi t) cos^2(pi t / 12) base / orig with
+                                 t = clamp((-p / new + (k - width) / orig) base, -6, 6), k in [0, 2 width + orig), and output sample
+                                 j new + p = sum_k c[p][k] xpad[j orig + k], xpad the 24 kHz waveform behind `width` zeros and followed
+                                 by zeros; n samples become ceil(n new / orig).  Computed on the GPU behind the vocoder in fp32 (one fma
+                                 chain per sample), after speed.  Decoding does not depend on it: tokens, aur_result.latents and
+                                 n_latent_rows are unchanged.  A result at 48000 pins twice the host bytes of one at 24000 */
     float speed;              /* speaking rate (new surface, like seed and priority; the reference's counterpart is a phase vocoder over
                                  the finished waveform, TTSOutput.change_speed).  0 = unset = 1.0; otherwise 0.5 <= speed <= 2.0, anything
                                  else (or a non-finite value) makes aur_submit fail with AUR_E_INVALID.  The XTTS inference(speed=) rule:
@@ -132,10 +143,11 @@ typedef struct aur_result {
     int32_t n_tokens;
     const int32_t* tokens;    /* mel token ids, stop id included when emitted */
     int32_t n_samples;
-    const float* wav;         /* 24 kHz mono PCM in [-1, 1] */
+    const float* wav;         /* mono PCM in [-1, 1] at `sample_rate` (a resampled waveform can overshoot the range by the filter's ripple) */
     int32_t n_latent_rows;
     const float* latents;     /* [n_tokens][1024] vocoder input (final_norm applied twice), may be NULL */
     int32_t error;            /* 0 or AUR_E_* if this sequence failed */
+    int32_t sample_rate;      /* of wav, in Hz: aur_seq_desc.sample_rate, 24000 when that was 0 */
 } aur_result;
 
 typedef struct aur_stats {
@@ -143,7 +155,7 @@ typedef struct aur_stats {
     int64_t prefill_rows;          /* prompt rows processed */
     int64_t decode_rows;           /* decode rows processed (one per live sequence per step) */
     int64_t tokens_generated;
-    int64_t samples_generated;
+    int64_t samples_generated;     /* as delivered, at each sequence's output rate */
     int64_t vocoder_batches;
     /* profile == 1 only: HIP-event time of the MFMA conv launches of the vocoder */
     int64_t conv_launches;
@@ -286,6 +298,11 @@ int aur_vocode(aur_engine* e, const float* latents, const int32_t* n_lat, int32_
  * speed == NULL is aur_vocode (which forwards here).  New surface; the reference has no counterpart. */
 int aur_vocode_speed(aur_engine* e, const float* latents, const int32_t* n_lat, const float* speed, int32_t B, int32_t t_max,
                      uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out);
+/* Same with an output sample rate per utterance, sample_rate[B] (aur_seq_desc.sample_rate: 0 = unset = 24000, else a supported rate);
+ * utterance b yields ceil(n new / orig) samples of the n that aur_vocode_speed yields, and wav_stride must hold the longest.
+ * sample_rate == NULL is aur_vocode_speed (which forwards here); speed == NULL as there. */
+int aur_vocode_rate(aur_engine* e, const float* latents, const int32_t* n_lat, const float* speed, const int32_t* sample_rate, int32_t B,
+                    int32_t t_max, uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out);
 
 int aur_sync(aur_engine* e);
 int aur_get_stats(aur_engine* e, aur_stats* out);
@@ -402,6 +419,11 @@ int aur_dbg_interp3(aur_engine* e, const float* lat, const int32_t* lat_row, con
 /* conv_post + tanh (conv_post_kernel): x [B][Cin][L] (x_f16_act: the activated halves form, `slope` unused), w [Cin][7], wav [B][L]. */
 int aur_dbg_conv_post(aur_engine* e, const float* x, const float* w, const int32_t* lens, int32_t B, int32_t Cin, int32_t L, float slope,
                       int32_t x_f16_act, float* wav, float guard_value, int64_t* guard_changed);
+/* The output-rate resampler alone (resample_out_kernel): x [B][L] 24 kHz rows of which lens[b] >= 1 samples count (what a row holds
+ * past them must not matter), rate[b] as aur_seq_desc.sample_rate; utterance b owns ceil(lens[b] new / orig) samples of out [B][Lout],
+ * Lout = the longest of them.  In / out sentinel and guards as above. */
+int aur_dbg_resample_out(aur_engine* e, const float* x, const int32_t* lens, const int32_t* rate, int32_t B, int32_t L, float* out,
+                         int32_t Lout, float guard_value, int64_t* guard_changed);
 /* Prefill one prompt and return ln_f rows [n_rows][1024] and the penalised logits [1026] of the last row. */
 int aur_dbg_prefill(aur_engine* e, const int32_t* text_ids, int32_t n_text, uint64_t speaker_key,
                     float repetition_penalty, float* lnf_rows_out, float* logits_out);
