@@ -1,6 +1,6 @@
 // What the translation units that define extern "C" entry points of include/auralis_amd.h share and the header does not export:
 // the mapping of exception types to AUR_E_* codes, and the engine state the kernel test harness (dbg_harness.hip) runs on (the host
-// rules of a launch it shares with the engine are gpt_host.h's and voc_net.h's).
+// rules of a launch it shares with the engine's networks, gpt_net.h and voc_net.h, are gpt_host.h's and voc_net.h's).
 #pragma once
 #include <new>
 #include <string>

@@ -6,7 +6,6 @@
 // Weight names and layouts: auralis_amd/weights.py: pack_conditioning.
 #pragma once
 #include <cmath>
-#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -26,9 +25,7 @@ struct CondParams {
 
 class CondNet {
 public:
-    using WeightFn = std::function<const float*(const std::string&, int64_t)>;
-    using HasFn = std::function<bool(const std::string&)>;
-    CondNet(WeightFn w, HasFn has, hipStream_t st) : W_(std::move(w)), has_(std::move(has)), st_(st) {}
+    CondNet(WeightTable& w, hipStream_t st) : W_(w), st_(st) {}
 
     // pcm: host pointers, mono float32 at 22 050 Hz; out_cond [32 * 1024], out_spk [512] (host)
     void run(const float* const* pcm, const int* n_samples, int n_refs, const CondParams& p, float* out_cond, float* out_spk) {
@@ -85,8 +82,7 @@ public:
     }
 
 private:
-    WeightFn W_;
-    HasFn has_;
+    WeightTable& W_;
     hipStream_t st_;
     std::vector<std::unique_ptr<DevBuf>> pool_;
     size_t used_ = 0;
@@ -98,7 +94,7 @@ private:
         b.ensure((size_t)std::max<long>(n, 1) * sizeof(float));
         return reinterpret_cast<float*>(b.p);
     }
-    const float* W(const std::string& n, int64_t numel = -1) { return W_(n, numel); }
+    const float* W(const std::string& n, int64_t numel = -1) { return W_.W(n, numel); }
     static int pad(int v, int m) { return (v + m - 1) / m * m; }
 
     // P[M][N] = X[M][K] . W[K][N]   (N, K as padded by the packer)
@@ -129,7 +125,7 @@ private:
         // NORMALISED input (AttentionBlock.forward :196-206)
         float* h = gemm(x0, 80, "cond.enc.init.w", T, 1024, 80);
         launch_cond_bias_act(h, 1024, W("cond.enc.init.b", 1024), T, 1024, 0, st_);
-        for (int i = 0; has_("cond.enc." + std::to_string(i) + ".qkv.w"); ++i) {
+        for (int i = 0; W_.has("cond.enc." + std::to_string(i) + ".qkv.w"); ++i) {
             const std::string p = "cond.enc." + std::to_string(i) + ".";
             float* xn = alloc((long)T * 1024);
             launch_cond_group_norm(h, xn, W(p + "gn.w", 1024), W(p + "gn.b", 1024), T, 1024, 32, st_);
@@ -153,7 +149,7 @@ private:
         const int L = 32, inner = 2730, inner_k = pad(inner, 16), ff_n = pad(2 * inner, 128);
         float* lat = alloc((long)L * 1024);
         HIP_CHECK(hipMemcpyAsync(lat, W("cond.per.latents", L * 1024), (size_t)L * 1024 * sizeof(float), hipMemcpyDeviceToDevice, st_));
-        for (int li = 0; has_("cond.per." + std::to_string(li) + ".q.w"); ++li) {
+        for (int li = 0; W_.has("cond.per." + std::to_string(li) + ".q.w"); ++li) {
             const std::string p = "cond.per." + std::to_string(li) + ".";
             float* ctx = alloc((long)(L + T) * 1024);
             HIP_CHECK(hipMemcpyAsync(ctx, lat, (size_t)L * 1024 * sizeof(float), hipMemcpyDeviceToDevice, st_));
@@ -226,7 +222,7 @@ private:
                 float* y2 = conv3(y, Ho, Wo, P, 1, p + "conv2.w", P, H2, W2);
                 launch_cond_bn(y2, (long)Ho * Wo, P, nullptr, W(p + "bn2.scale", P), W(p + "bn2.shift", P), 0, 0, st_);
                 const float* res = cur;
-                if (has_(p + "down.w")) {
+                if (W_.has(p + "down.w")) {
                     float* rows = alloc((long)Ho * Wo * C);
                     launch_cond_gather_stride(cur, H, Wd, C, stride, rows, Ho, Wo, st_);
                     float* d = gemm(rows, C, p + "down.w", Ho * Wo, P, C);

@@ -1,5 +1,8 @@
-// Host-only RAII wrappers of device and pinned host allocations and the profilers' event pool, shared by every host translation unit.
+// Host-only RAII wrappers of device and pinned host allocations, the table of loaded weights and the profilers' event pool, shared by every host translation unit.
 #pragma once
+#include <memory>
+#include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "common.h"
@@ -64,6 +67,31 @@ struct PinBuf {
     template <class T>
     T* as() const {
         return reinterpret_cast<T*>(p);
+    }
+};
+
+// The loaded checkpoint: tensor name -> fp32 device buffer.  The engine fills it (aur_load_weights); the networks look their weights up
+// in it when they bind.
+struct Tensor {
+    std::unique_ptr<DevBuf> buf;
+    int64_t numel = 0;
+    bool f16_eff = false;   // aur_config.gpt_fp16: the buffer holds the effective weights W'' (a per-layer matrix), or the LayerNorm
+                            // gain they were derived with, since the last load of this tensor
+    float* d() const { return buf->as<float>(); }
+};
+struct WeightTable {
+    std::unordered_map<std::string, Tensor> map;
+    bool has(const std::string& name) const { return map.find(name) != map.end(); }
+    Tensor& at(const std::string& name) {
+        auto it = map.find(name);
+        if (it == map.end()) throw StateError("weight not loaded: " + name);
+        return it->second;
+    }
+    const float* W(const std::string& name, int64_t numel = -1) {
+        const Tensor& t = at(name);
+        if (numel >= 0 && t.numel != numel)
+            throw InvalidArgument("weight " + name + " has " + std::to_string(t.numel) + " elements, expected " + std::to_string(numel));
+        return t.d();
     }
 };
 

@@ -1,29 +1,27 @@
 // Host runtime + C ABI (include/auralis_amd.h) of the MI355X-native XTTSv2 hot path.
 //
-// One Engine per GPU/process.  It owns: the packed weights, a paged KV pool with a block allocator, the
-// per-slot device state of the continuous batcher, the latent stash that replaces the reference's second
-// GPT pass (XTTSv2.py:617-687; equivalence argued in SURVEY.md §7 and tested in tests/), and the vocoder
-// workspace.  The reference's counterparts are vLLM's AsyncLLMEngine/scheduler/block manager (un-vendored,
-// XTTSv2.py:198-232), HiddenStatesCollector (components/vllm/hidden_state_collector.py) and the
-// asyncio.to_thread HiFi-GAN call (XTTSv2.py:804).
+// One Engine per GPU/process.  It owns the loaded weights, the continuous batcher (admission, the K/V block allocator, the sequences
+// and their slots, the pipelined decode loop), the speaker table, the latent pool and the vocoder stage.  The three networks live apart
+// from it: the GPT with its K/V pool, per-slot device state and the latent stash that replaces the reference's second GPT pass
+// (XTTSv2.py:617-687; equivalence argued in SURVEY.md §7 and tested in tests/) in gpt_net.h, the vocoder in voc_net.h, conditioning in
+// cond_net.h.  The reference's counterparts are vLLM's AsyncLLMEngine/scheduler/block manager (un-vendored, XTTSv2.py:198-232),
+// HiddenStatesCollector (components/vllm/hidden_state_collector.py) and the asyncio.to_thread HiFi-GAN call (XTTSv2.py:804).
 #include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstring>
 #include <deque>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "abi_internal.h"
 #include "cond_net.h"
-#include "gpt_host.h"
+#include "gpt_net.h"
 #include "voc_net.h"
 
 namespace aur {
@@ -31,66 +29,12 @@ namespace aur {
 thread_local std::string g_last_error;
 
 constexpr int kProfileEvery = 64;   // profile mode default: every 64th decode step is followed by the per-kind replay batches (profile_replay)
-constexpr int kProj2Slabs = 4;   // split-K slabs of the prompt-row MLP projection (forward_rows)
 
 // Pinned result block of one vocoder batch: the D2H copies land here and aur_result.wav / .latents point straight into
 // it (no second host copy); the block returns to the pool when the last sequence of the batch is released.
 struct PinBlock {
     PinBuf buf;
     int refs = 0;
-};
-
-struct Tensor {
-    std::unique_ptr<DevBuf> buf;
-    int64_t numel = 0;
-    bool f16_eff = false;   // aur_config.gpt_fp16: the buffer holds the effective weights W'' (a per-layer matrix), or the LayerNorm
-                            // gain they were derived with, since the last load of this tensor
-    float* d() const { return buf->as<float>(); }
-};
-
-struct SlotInit {
-    int slot;
-    float temperature, top_p;
-    int top_k;
-    float rep_penalty;
-    int max_tokens, ignore_stop;
-    unsigned seed;
-    int ngen;   // initial n_gen (0; dbg_sample injects a step)
-};
-
-__global__ __launch_bounds__(256) void init_slots_kernel(const SlotInit* __restrict__ init, int* slot_tok,
-                                                         int* slot_pos, int* slot_kvpos, int* slot_ngen,
-                                                         int* slot_finished, float* temperature, float* top_p,
-                                                         int* top_k, float* rep, int* max_tokens, int* ignore_stop,
-                                                         unsigned* seed, unsigned char* seen, int start_token) {
-    const SlotInit s = init[blockIdx.x];
-    unsigned char* row = seen + (long)s.slot * kSeenStride;
-    for (int i = threadIdx.x; i < kSeenStride; i += 256) row[i] = (i == 1 || i == start_token) ? 1 : 0;
-    if (threadIdx.x == 0) {
-        slot_tok[s.slot] = start_token;
-        slot_pos[s.slot] = 0;
-        slot_kvpos[s.slot] = 0;
-        slot_ngen[s.slot] = s.ngen;
-        slot_finished[s.slot] = 0;
-        temperature[s.slot] = s.temperature;
-        top_p[s.slot] = s.top_p;
-        top_k[s.slot] = s.top_k;
-        rep[s.slot] = s.rep_penalty;
-        max_tokens[s.slot] = s.max_tokens;
-        ignore_stop[s.slot] = s.ignore_stop;
-        seed[s.slot] = s.seed;
-    }
-}
-
-// Row workspace of one GPT forward chain (prefill uses chain 0; decode can run two chains on two streams).
-struct RowWs {
-    hipStream_t st = nullptr;
-    int rows_cap = 0;
-    DevBuf h, xn, qbuf, att, act, P, P2, ybuf, stats, row_meta;   // row_meta: per-row K/V addressing of the current decode step   // stats: LayerNorm partials of the packed residual stream [rows][64] float2
-    DevBuf i_row_slot, i_row_pos, i_desc, i_sample_row, i_sample_slot, i_next_kvpos, i_out_tok, i_qblk;
-    std::vector<int2> h_qblk;   // query blocks of the prompt rows in flight (launch_prompt_attention)
-    PinBuf pin;
-    std::vector<int> sample_row, sample_slot;
 };
 
 enum class SeqState { WAITING, RUNNING, TOKENS_DONE, DONE, RELEASED };
@@ -132,66 +76,48 @@ public:
         if (cfg_.max_speakers <= 0) cfg_.max_speakers = 64;
         const int S = cfg_.max_seqs;
         n_blocks_ = (long)S * kMaxBlocks + 2L * cfg_.max_speakers;   // + 2 shared prefix blocks per speaker
-        kv_layer_stride_ = n_blocks_ * kKvBlockElems;
-        kv_half_ = cfg_.kv_fp16 != 0;
+        const bool kv_half = cfg_.kv_fp16 != 0;
         // paged_attention_kernel addresses a layer's pool with 32-bit byte offsets: 494 slots with the fp32 pool, 991 with fp16
         // (at 30 layers that is 120 GiB of K/V; HBM holds ~1000 slots' worth next to the weights)
         {
-            const long cap = kv_half_ ? 2 * kMaxKvBlocksPerLayer + 1 : kMaxKvBlocksPerLayer;
+            const long cap = kv_half ? 2 * kMaxKvBlocksPerLayer + 1 : kMaxKvBlocksPerLayer;
             if (n_blocks_ > cap)
                 throw InvalidArgument("requirement failed: K/V pool: a layer's pool must stay below 4 GiB; with max_speakers = " +
-                                      std::to_string(cfg_.max_speakers) + (kv_half_ ? " and kv_fp16" : " and the fp32 pool") + " max_seqs <= " +
+                                      std::to_string(cfg_.max_speakers) + (kv_half ? " and kv_fp16" : " and the fp32 pool") + " max_seqs <= " +
                                       std::to_string((cap - 2L * cfg_.max_speakers) / kMaxBlocks) + " (asked for " + std::to_string(S) + ")");
         }
-        gemm_prec_ = cfg_.gemm_f32_exact ? 0 : 1;
-        gpt_f16_ = cfg_.gpt_fp16 != 0;
-        AUR_REQUIRE(!(gpt_f16_ && cfg_.gemm_f32_exact), "gpt_fp16 and gemm_f32_exact exclude each other (the fp16-weight decode GEMMs "
-                                                        "run on the split arithmetic)");
-        kv_.ensure((size_t)cfg_.n_layer * kv_layer_stride_ * (kv_half_ ? 2 : 4));
+        AUR_REQUIRE(!(cfg_.gpt_fp16 && cfg_.gemm_f32_exact), "gpt_fp16 and gemm_f32_exact exclude each other (the fp16-weight decode GEMMs "
+                                                             "run on the split arithmetic)");
+        GptLayout gl{cfg_.n_layer, S, n_blocks_, cfg_.gemm_f32_exact ? 0 : 1, cfg_.gpt_fp16 != 0, true, kv_half, cfg_.gelu_erf != 0, false};
+        if (const char* e = getenv("AUR_GEMM_PRESPLIT")) gl.presplit = atoi(e) != 0; // 0: prompt-row GEMMs split their weights per tile instead of reading the planes packed at load time (A/B only)
+        if (const char* e = getenv("AUR_SAMPLER_FULL_SORT")) gl.sampler_full_sort = atoi(e) != 0;
+        gpt_.reset(new GptNet(w_, st_, gl));
         for (int b = (int)n_blocks_ - 1; b >= 0; --b) free_blocks_.push_back(b);
-        auto ints = [&](DevBuf& b, size_t n) {
-            b.ensure(n * sizeof(int));
-            HIP_CHECK(hipMemsetAsync(b.p, 0, n * sizeof(int), st_));
-        };
-        ints(slot_tok_, S); ints(slot_pos_, S); ints(slot_kvpos_, S); ints(slot_ngen_, S); ints(slot_finished_, S);
-        ints(temperature_, S); ints(top_p_, S); ints(top_k_, S); ints(rep_, S); ints(max_tokens_, S);
-        ints(ignore_stop_, S); ints(seed_, S);
-        ints(block_tables_, (size_t)(S + 1) * kMaxBlocks);   // row S: pseudo-slot used to prefill a speaker prefix
-        seen_.zeros((size_t)S * kSeenStride, st_);
-        latents_.ensure((size_t)S * kMaxLatRows * kHidden * sizeof(float));
         spk_table_.ensure((size_t)cfg_.max_speakers * 32 * kHidden * sizeof(float));
         spk_emb_.ensure((size_t)cfg_.max_speakers * 512 * sizeof(float));
         voc_cond_.ensure((size_t)cfg_.max_speakers * kCondStride * sizeof(float));
-        zero_bias_.zeros(4096 * sizeof(float), st_);
-        ksp_buf_.ensure((size_t)kGemmKspTiles * 16 * 256 * sizeof(float));   // K-split partial tiles of the small-M mlp projection
-        ksp_cnt_.zeros((size_t)kGemmKspTiles * sizeof(unsigned), st_);
         h_block_tables_.assign((size_t)(S + 1) * kMaxBlocks, 0);
         spk_info_.assign(cfg_.max_speakers, SpeakerInfo{});
         slot_owner_.assign(S, nullptr);
-        HIP_CHECK(hipStreamCreateWithPriority(&st2_, hipStreamDefault, prio_hi));
         HIP_CHECK(hipStreamCreateWithPriority(&st_voc_, hipStreamDefault, prio_lo));
         HIP_CHECK(hipEventCreateWithFlags(&ev_lat_, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&ev_voc_done_, hipEventDisableTiming));
         HIP_CHECK(hipEventRecord(ev_lat_, st_));
         latpool_.ensure((size_t)2 * S * kMaxLatRows * kHidden * sizeof(float));
         for (int i = 2 * S - 1; i >= 0; --i) latpool_free_.push_back(i);
-        ws_[0].st = st_;
-        ws_[1].st = st2_;
         VocLayout lay{cfg_.vocoder_fp16 != 0, cfg_.vocoder_fp16 != 0, true};
         if (const char* e = getenv("AUR_XT_F16")) lay.halves = lay.halves && atoi(e) != 0;   // 0: fp32 ResBlock intermediates and residual stream (A/B only)
         if (const char* e = getenv("AUR_CONV_DMA")) lay.dma = atoi(e) != 0;   // 0: register-staged ResBlock convs (A/B only)
-        voc_.reset(new HifiGan([this](const std::string& n) { return W(n); }, st_voc_, lay));
-        if (const char* e = getenv("AUR_GEMM_PRESPLIT")) gemm_presplit_ = atoi(e) != 0; // 0: prompt-row GEMMs split their weights per tile instead of reading the planes packed at load time (A/B only)
+        voc_.reset(new HifiGan(w_, st_voc_, lay));
         if (const char* e = getenv("AUR_DECODE_PIPELINE")) pipeline_ = atoi(e) != 0;
-        if (const char* e = getenv("AUR_SAMPLER_FULL_SORT")) sampler_full_sort_ = atoi(e) != 0;
         if (const char* e = getenv("AUR_HOST_TRACE")) host_trace_ = atoi(e) != 0;
         if (const char* e = getenv("AUR_TEST_FAIL_STEP")) fail_at_step_ = atoi(e);
         if (const char* e = getenv("AUR_TEST_FAIL_VOC")) fail_at_voc_ = atoi(e);
 
-        for (int i = 0; i < 2; ++i) {
-            HIP_CHECK(hipEventCreateWithFlags(&ev_rb_[i], hipEventDisableTiming));
-            HIP_CHECK(hipEventCreate(&ev_ds_[i]));
-            HIP_CHECK(hipEventCreate(&ev_de_[i]));
+        for (StepEvents& ev : ev_step_) {
+            HIP_CHECK(hipEventCreateWithFlags(&ev.readback, hipEventDisableTiming));
+            HIP_CHECK(hipEventCreate(&ev.start));
+            HIP_CHECK(hipEventCreate(&ev.end));
         }
         HIP_CHECK(hipEventCreate(&ev_a_));
         HIP_CHECK(hipEventCreate(&ev_b_));
@@ -201,27 +127,25 @@ public:
         (void)hipSetDevice(device_);
         (void)hipStreamSynchronize(st_);
         (void)hipStreamSynchronize(st_voc_);
-        for (auto& e : gemm_events_) {
-            (void)hipEventDestroy(e.a);
-            (void)hipEventDestroy(e.b);
-        }
         (void)hipEventDestroy(ev_a_);
         (void)hipEventDestroy(ev_b_);
-        for (int i = 0; i < 2; ++i) {
-            (void)hipEventDestroy(ev_rb_[i]);
-            (void)hipEventDestroy(ev_ds_[i]);
-            (void)hipEventDestroy(ev_de_[i]);
+        for (StepEvents& ev : ev_step_) {
+            (void)hipEventDestroy(ev.readback);
+            (void)hipEventDestroy(ev.start);
+            (void)hipEventDestroy(ev.end);
         }
         if (comm_) (void)Rccl::get().CommDestroy(comm_);
         (void)hipEventDestroy(ev_lat_);
         (void)hipEventDestroy(ev_voc_done_);
         (void)hipStreamDestroy(st_voc_);
-        (void)hipStreamDestroy(st2_);
         (void)hipStreamDestroy(st_);
     }
 
     void use() { HIP_CHECK(hipSetDevice(device_)); }
-    DbgCtx dbg_ctx() const { return {device_, st_, st_voc_, gemm_prec_, gpt_f16_, gemm_presplit_, ksp_buf_.as<float>(), ksp_cnt_.as<unsigned>()}; }
+    DbgCtx dbg_ctx() const {
+        const GptLayout& g = gpt_->layout();
+        return {device_, st_, st_voc_, g.prec, g.f16, g.presplit, gpt_->ksp_buf(), gpt_->ksp_cnt()};
+    }
 
     // ------------------------------------------------------------------ weights
     void load(const aur_tensor_desc* t, size_t n) {
@@ -230,52 +154,17 @@ public:
         std::lock_guard<std::mutex> lk(mu_);       // submit() reads the table sizes under mu_
         for (size_t i = 0; i < n; ++i) {
             AUR_REQUIRE(t[i].name && t[i].data && t[i].numel > 0, "bad tensor desc");
-            Tensor& dst = w_[t[i].name];
+            Tensor& dst = w_.map[t[i].name];
             if (!dst.buf) dst.buf.reset(new DevBuf());
             dst.buf->upload(t[i].data, (size_t)t[i].numel * sizeof(float));
             dst.numel = t[i].numel;
             dst.f16_eff = false;
         }
         voc_->unbind();
-        gpt_ready_ = false;
-        if (gpt_f16_) check_gpt_f16();
+        gpt_->unbind();
+        if (cfg_.gpt_fp16) gpt_->check_f16();
     }
-    // The four linears of a GPT layer, in the order the decode chain runs them: tensor name (.w / .b) under the layer's prefix, the
-    // LayerNorm in front of it (folded into its decode operand) or none, and its shape.
-    struct LinearSpec {
-        const char *name, *ln;
-        int K, N;
-    };
-    static constexpr LinearSpec kLinears[4] = {{"attn.c_attn", "ln_1", kHidden, 3 * kHidden}, {"attn.c_proj", nullptr, kHidden, kHidden},
-                                               {"mlp.c_fc", "ln_2", kHidden, 4 * kHidden}, {"mlp.c_proj", nullptr, 4 * kHidden, kHidden}};
-    static std::string layer_prefix(int i) { return "gpt.h." + std::to_string(i) + "."; }
-    // aur_config.gpt_fp16: once every per-layer matrix and its LayerNorm gain are loaded, a matrix the rule rejects (not finite, or
-    // beyond the fp16 range after folding) fails the load that completed the set, before anything is converted
-    void check_gpt_f16() {
-        auto has = [&](const std::string& n, int64_t numel) { auto it = w_.find(n); return it != w_.end() && it->second.numel == numel; };
-        for (int i = 0; i < cfg_.n_layer; ++i)
-            for (const LinearSpec& m : kLinears)   // not complete yet (or misshapen: ensure_gpt reports that)
-                if (!has(layer_prefix(i) + m.name + ".w", (int64_t)m.K * m.N) || (m.ln && !has(layer_prefix(i) + m.ln + ".w", m.K))) return;
-        DevBuf dbad, scratch;
-        dbad.zeros(sizeof(int), st_);
-        scratch.ensure((size_t)4 * kHidden * kHidden * 2);
-        for (int i = 0; i < cfg_.n_layer; ++i)
-            for (const LinearSpec& m : kLinears)
-                launch_pack_wt16_f16(W(layer_prefix(i) + m.name + ".w"), m.N, m.ln ? W(layer_prefix(i) + m.ln + ".w") : nullptr, nullptr, scratch.p,
-                                     dbad.as<int>(), m.K, m.N, st_);
-        int bad = 0;
-        HIP_CHECK(hipMemcpyAsync(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost, st_));
-        HIP_CHECK(hipStreamSynchronize(st_));
-        if (bad) throw InvalidArgument("gpt_fp16: a per-layer GPT linear is not finite or leaves the fp16 range after LayerNorm folding");
-    }
-    const float* W(const std::string& name, int64_t numel = -1) const {
-        auto it = w_.find(name);
-        if (it == w_.end()) throw StateError("weight not loaded: " + name);
-        if (numel >= 0 && it->second.numel != numel)
-            throw InvalidArgument("weight " + name + " has " + std::to_string(it->second.numel) + " elements, expected " +
-                                  std::to_string(numel));
-        return it->second.d();
-    }
+    void ensure_gpt() { gpt_->bind(), voc_->bind(); }   // the layer tables out of what is loaded (no-ops once bound; load() unbinds)
 
     // ------------------------------------------------------------------ conditioning
     // Speaker table (caller holds mu_).  A row is pinned while any sequence submitted with it has not been delivered yet
@@ -438,11 +327,8 @@ public:
                               float* out_spk) {
         std::lock_guard<std::mutex> gl(gpu_mu_);   // shares the GPT stream; not while a step is running
         use();
-        if (!cond_net_) {
-            cond_net_.reset(new CondNet([this](const std::string& n, int64_t numel) { return W(n, numel); },
-                                        [this](const std::string& n) { return w_.find(n) != w_.end(); }, st_));
-        }
-        AUR_REQUIRE(w_.find("cond.enc.init.w") != w_.end(), "conditioning weights not loaded (pack_conditioning)");
+        if (!cond_net_) cond_net_.reset(new CondNet(w_, st_));
+        AUR_REQUIRE(w_.has("cond.enc.init.w"), "conditioning weights not loaded (pack_conditioning)");
         CondParams p;
         p.max_ref_length = cp.max_ref_length;
         p.gpt_cond_len = cp.gpt_cond_len;
@@ -469,12 +355,12 @@ public:
         // 1x1 conditioning convs of the vocoder on the speaker embedding (hifigan_decoder.py:243-251)
         float* dst = voc_cond_.as<float>() + (long)row * kCondStride;
         const float* g = spk_emb_.as<float>() + (long)row * 512;
-        launch_gemv_rows(W("voc.cond_layer.w", 512 * 512), W("voc.cond_layer.b", 512), g, dst, 512, 512, 1, 0, 0, st_);
+        launch_gemv_rows(w_.W("voc.cond_layer.w", 512 * 512), w_.W("voc.cond_layer.b", 512), g, dst, 512, 512, 1, 0, 0, st_);
         int off = 512;
         for (int i = 0; i < 4; ++i) {
             const int C = kVocChans[i];
             const std::string p = "voc.conds." + std::to_string(i);
-            launch_gemv_rows(W(p + ".w", (int64_t)C * 512), W(p + ".b", C), g, dst + off, C, 512, 1, 0, 0, st_);
+            launch_gemv_rows(w_.W(p + ".w", (int64_t)C * 512), w_.W(p + ".b", C), g, dst + off, C, 512, 1, 0, 0, st_);
             off += C;
         }
         HIP_CHECK(hipStreamSynchronize(st_));
@@ -487,7 +373,7 @@ public:
     void prefill_speaker_prefix(int row) {
         SpeakerInfo& si = spk_info_[row];
         si.ready = false;
-        if (w_.find("gpt.wte") == w_.end()) return;   // GPT weights not loaded yet: unshared path
+        if (!w_.has("gpt.wte")) return;   // GPT weights not loaded yet: unshared path
         ensure_gpt();
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -499,8 +385,6 @@ public:
                 }
             }
         }
-        RowWs& w = ws_[0];
-        last_active_.clear();
         const int S = cfg_.max_seqs;
         std::vector<int4> desc;
         std::vector<int> row_slot(32, S), row_pos(32);
@@ -508,16 +392,11 @@ public:
             desc.push_back(make_int4(0, i, row, 0));
             row_pos[i] = i;
         }
-        ensure_rows(w, 32);
         h_block_tables_[(size_t)S * kMaxBlocks + 0] = si.blocks[0];
         h_block_tables_[(size_t)S * kMaxBlocks + 1] = si.blocks[1];
-        HIP_CHECK(hipMemcpyAsync(block_tables_.p, h_block_tables_.data(), h_block_tables_.size() * 4, hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_desc.p, desc.data(), 32 * sizeof(int4), hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_row_slot.p, row_slot.data(), 32 * 4, hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_row_pos.p, row_pos.data(), 32 * 4, hipMemcpyHostToDevice, w.st));
-        launch_embed_prompt(w.i_desc.as<int4>(), spk_table_.as<float>(), text_emb_, text_pos_, wte_, wpe_, w.h.as<float>(), 32, w.st);
-        forward_rows(w, 32, w.i_row_slot.as<int>(), w.i_row_pos.as<int>(), upload_qblocks(w, row_slot, row_pos));
-        HIP_CHECK(hipStreamSynchronize(w.st));
+        gpt_->upload_block_tables(h_block_tables_);
+        gpt_->prompt_rows(desc, row_slot, row_pos, spk_table_.as<float>());
+        HIP_CHECK(hipStreamSynchronize(st_));
         si.ready = true;
     }
 
@@ -533,9 +412,8 @@ public:
         AUR_REQUIRE(rate_class(d.sample_rate) >= 0, "sample_rate is 0 (unset) or one of 8000, 16000, 22050, 24000, 32000, 44100, 48000");
         std::lock_guard<std::mutex> lk(mu_);
         {   // reject bad text ids / positions here, not in the middle of a batched prefill
-            auto te = w_.find("text_emb"), tp = w_.find("text_pos");
-            if (te == w_.end() || tp == w_.end()) throw StateError("weights not loaded");
-            const int vocab = (int)(te->second.numel / kHidden), npos = (int)(tp->second.numel / kHidden);
+            if (!w_.has("text_emb") || !w_.has("text_pos")) throw StateError("weights not loaded");
+            const int vocab = (int)(w_.at("text_emb").numel / kHidden), npos = (int)(w_.at("text_pos").numel / kHidden);
             AUR_REQUIRE(d.n_text <= npos, "text longer than the text position table");
             for (int i = 0; i < d.n_text; ++i) AUR_REQUIRE(d.text_ids[i] >= 0 && d.text_ids[i] < vocab, "text id out of range");
         }
@@ -629,7 +507,7 @@ public:
             Seq* s = it->second.get();
             if (s->state == SeqState::RUNNING && s->slot >= 0 && !s->cancel) {
                 s->cancel = true;
-                HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(max_tokens_.as<int>() + s->slot), 1, 1, st_));
+                gpt_->limit_tokens(s->slot);
             } else if (s->state == SeqState::TOKENS_DONE) {
                 auto q = std::find(voc_queue_.begin(), voc_queue_.end(), s);
                 if (q != voc_queue_.end()) {
@@ -665,11 +543,9 @@ public:
         (void)hipStreamSynchronize(st_);
         (void)hipStreamSynchronize(st_voc_);
         (void)hipGetLastError();
-        (void)hipMemsetAsync(ksp_cnt_.p, 0, (size_t)kGemmKspTiles * sizeof(unsigned), st_);   // an aborted K-split launch may have left tickets behind
+        gpt_->reset_after_failure();
         infl_.on = false;
         just_finished_.clear();
-        last_active_.clear();
-        n_gemm_events_ = 0;
         voc_->drop_events();
         std::lock_guard<std::mutex> lk(mu_);
         auto fail = [&](Seq* s) {
@@ -954,21 +830,20 @@ public:
         d.text_ids = text_ids; d.n_text = n_text; d.speaker_key = key; d.temperature = 0.f; d.top_p = 1.f; d.top_k = -1;
         d.repetition_penalty = rep_penalty; d.max_tokens = 1; d.seed = 0; d.ignore_stop = 1;
         const uint64_t id = submit(d);
-        dbg_logits_.ensure((size_t)kMelVocab * 4);
         {
             struct Restore {   // also when the step throws
                 Engine& e;
-                ~Restore() { e.share_prefix_now_ = true, e.dbg_capture_ = false; }
+                ~Restore() { e.share_prefix_now_ = true, e.gpt_->set_capture(false); }
             } restore{*this};
-            dbg_capture_ = true;
+            gpt_->set_capture(true);
             share_prefix_now_ = false;
             step(nullptr, nullptr);
         }
         for (int guard = 0; guard < 1000 && seqs_.at(id)->state != SeqState::DONE; ++guard) step(nullptr, nullptr);
         Seq* s = seqs_.at(id).get();
         if (lnf_rows_out)
-            HIP_CHECK(hipMemcpy(lnf_rows_out, dbg_lnf_.p, (size_t)s->n_prompt * kHidden * 4, hipMemcpyDeviceToHost));
-        if (logits_out) HIP_CHECK(hipMemcpy(logits_out, dbg_logits_.p, (size_t)kMelVocab * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(lnf_rows_out, gpt_->dbg_lnf(), (size_t)s->n_prompt * kHidden * 4, hipMemcpyDeviceToHost));
+        if (logits_out) HIP_CHECK(hipMemcpy(logits_out, gpt_->dbg_logits(), (size_t)kMelVocab * 4, hipMemcpyDeviceToHost));
         aur_result r;
         while (poll(&r, 1) == 1) {
         }
@@ -979,40 +854,10 @@ public:
         use();
         AUR_REQUIRE(idle(), "dbg_sample needs an idle engine");
         AUR_REQUIRE(B >= 1 && B <= cfg_.max_seqs, "B <= max_seqs");
-        std::vector<SlotInit> init(B);
-        std::vector<int> slots(B);
-        for (int b = 0; b < B; ++b) {
-            init[b] = SlotInit{b, temperature, top_p, top_k, rep, 1 << 30, 1, seed + (unsigned)b, step_idx};
-            slots[b] = b;
-        }
-        init_slots(init);
-        if (seen) {
-            for (int b = 0; b < B; ++b)
-                HIP_CHECK(hipMemcpyAsync(seen_.as<unsigned char>() + (long)b * kSeenStride, seen + (long)b * kMelVocab,
-                                         kMelVocab, hipMemcpyHostToDevice, st_));
-        } else {
-            HIP_CHECK(hipMemsetAsync(seen_.p, 0, (size_t)B * kSeenStride, st_));
-        }
-        DevBuf dl;
-        dl.ensure((size_t)B * kMelVocab * 4);
-        HIP_CHECK(hipMemcpyAsync(dl.p, logits, (size_t)B * kMelVocab * 4, hipMemcpyHostToDevice, st_));
-        RowWs& w = ws_[0];
-        w.i_sample_slot.ensure(B * 4);
-        w.i_out_tok.ensure(B * 4);
-        HIP_CHECK(hipMemcpyAsync(w.i_sample_slot.p, slots.data(), B * 4, hipMemcpyHostToDevice, st_));
-        SamplerArgs a = sampler_args(w, dl.as<float>(), 1, B, kMelVocab, zero_bias_.as<float>(), nullptr);
-        launch_sampler(a, st_);
-        HIP_CHECK(hipStreamSynchronize(st_));
-        HIP_CHECK(hipMemcpy(tokens_out, w.i_out_tok.p, B * 4, hipMemcpyDeviceToHost));
-        for (int b = 0; b < B; ++b)
-            if (tokens_out[b] >= 0) tokens_out[b] &= ~kTokFinishedBit;
+        gpt_->dbg_sample(logits, B, temperature, top_p, top_k, rep, seen, seed, step_idx, tokens_out);
     }
 
 private:
-    static constexpr int kMaxLatRows = 608;
-    static constexpr int kMelVocab = 1026;
-    static constexpr int kHeadPad = 1088;         // mel_head columns padded to a multiple of 64
-    static constexpr int kStartToken = 1024, kStopToken = 1025;
     bool idle() {
         std::lock_guard<std::mutex> lk(mu_);
         if (!waiting_.empty() || !voc_queue_.empty() || voc_active_ || infl_.on) return false;
@@ -1021,373 +866,22 @@ private:
         return true;
     }
 
-    // ------------------------------------------------------------------ GPT
-    struct Linear {   // one entry of kLinears in one layer
-        const float *w, *b;       // the loaded [K][N] matrix (aur_config.gpt_fp16: W'' once ensure_gpt has run) and bias
-        const float *lnw, *lnb;   // gain and shift of the LayerNorm in front of it, or null
-        int K, N;
-        DecodeOperand op;    // decode-regime GEMM (gemm_rows_kernel): packed weights, c1, effective bias (prepare_decode_operand)
-        const void* split;   // prefill-regime GEMM: the three bf16 planes of launch_pack_wsplit (only the split arithmetic uses them)
-    };
-    enum { kQkv, kProj, kFc, kProj2 };   // indices into kLinears / LayerW::lin, = the GEMM kind of the decode profile
-    struct LayerW {
-        Linear lin[4];
-    };
-    void ensure_gpt() {
-        if (gpt_ready_) return;
-        layers_.clear();
-        packed_.clear();
-        const int H = kHidden;
-        // aur_config.gpt_fp16: fp16 decode operands by the rule of launch_pack_wt16_f16; the matrices themselves are replaced by W'' in
-        // place, so the prompt-row GEMMs (their pre-split planes are taken afterwards) and second_pass run on the same effective
-        // weights.  Converting W'' again gives the same bits.
-        DevBuf dbad;   // (never read: check_gpt_f16 has checked before anything is converted)
-        if (gpt_f16_) {
-            check_gpt_f16();
-            dbad.ensure(sizeof(int));
-        }
-        for (int i = 0; i < cfg_.n_layer; ++i) {
-            const std::string p = layer_prefix(i);
-            layers_.emplace_back();
-            for (int k = 0; k < 4; ++k) {
-                const LinearSpec& m = kLinears[k];
-                const std::string wn = p + m.name + ".w", gn = m.ln ? p + m.ln + ".w" : "";
-                Linear& L = layers_.back().lin[k];
-                L.K = m.K; L.N = m.N;
-                L.w = W(wn, (int64_t)m.K * m.N); L.b = W(p + m.name + ".b", m.N);
-                L.lnw = m.ln ? W(gn, m.K) : nullptr; L.lnb = m.ln ? W(p + m.ln + ".b", m.K) : nullptr;
-                if (gpt_f16_ && m.ln && w_.at(wn).f16_eff && !w_.at(gn).f16_eff)
-                    throw StateError("gpt_fp16: " + gn + " was loaded again after " + wn + " was converted with the previous "
-                                     "one; load " + wn + " again as well");
-                L.op = prepare_decode_operand(gpt_f16_ ? 2 : gemm_prec_, L.w, m.N, L.lnw, L.lnb, L.b, m.K, m.N, w_.at(wn).d(), dbad.as<int>(),
-                                              fold_scratch_, packed_, st_);
-                if (gpt_f16_) w_.at(wn).f16_eff = true;
-                if (gpt_f16_ && m.ln) w_.at(gn).f16_eff = true;
-                L.split = nullptr;
-                if (gemm_prec_ == 1 && gemm_presplit_) {
-                    packed_.emplace_back(new DevBuf());
-                    packed_.back()->ensure((size_t)3 * m.K * m.N * 2);
-                    launch_pack_wsplit(L.w, m.N, packed_.back()->p, m.K, m.N, st_);
-                    L.split = packed_.back()->p;
-                }
-            }
-        }
-        wte_ = W("gpt.wte", (int64_t)kMelVocab * H);
-        wpe_ = W("gpt.wpe", (int64_t)kMaxLatRows * H);
-        lnfw_ = W("gpt.ln_f.w", H); lnfb_ = W("gpt.ln_f.b", H);
-        fnw_ = W("final_norm.w", H); fnb_ = W("final_norm.b", H);
-        headT_ = W("mel_head.wT", (int64_t)H * kHeadPad);
-        headb_ = W("mel_head.b", kHeadPad);
-        thead_ = prepare_decode_operand(gemm_prec_, headT_, kHeadPad, nullptr, nullptr, nullptr, H, kHeadPad, nullptr, nullptr, fold_scratch_,
-                                        packed_, st_).Wt;
-        HIP_CHECK(hipStreamSynchronize(st_));
-        fold_scratch_.release();
-        text_emb_ = W("text_emb");
-        text_pos_ = W("text_pos");
-        text_vocab_ = (int)(w_.at("text_emb").numel / H);
-        text_positions_ = (int)(w_.at("text_pos").numel / H);
-        voc_->bind();
-        gpt_ready_ = true;
-    }
-    void ensure_rows(RowWs& w, int M) {
-        if (M <= w.rows_cap) return;
-        last_active_.clear();   // buffers move: the row indices have to be uploaded again
-        const int cap = (std::max(M, 64) + 63) / 64 * 64;   // whole 64-row groups: the decode chain keeps its rows packed (pk_off)
-        w.ybuf.ensure((size_t)cap * kHidden * 4);
-        w.stats.ensure((size_t)cap * 64 * sizeof(float2));
-        w.row_meta.ensure((size_t)cap * kRowMetaStride * sizeof(int));
-        // embed_decode writes entries [0, kRowMetaBt + max_blocks) of the live rows only; the look-ahead entries behind them and the rows
-        // >= M of the last tile are READ (their values discarded by selects): defined zeros, not whatever the allocation held
-        HIP_CHECK(hipMemsetAsync(w.row_meta.p, 0, (size_t)cap * kRowMetaStride * sizeof(int), w.st));
-        w.h.ensure((size_t)cap * kHidden * 4);
-        w.xn.ensure((size_t)cap * kHidden * 4);
-        w.qbuf.ensure((size_t)cap * kHidden * 4);
-        w.att.ensure((size_t)cap * kHidden * 4);
-        w.act.ensure((size_t)cap * 4 * kHidden * 4);
-        w.P.ensure((size_t)cap * 4096 * 4);   // one GEMM output slab (prefill)
-        w.i_row_slot.ensure((size_t)cap * 4);
-        w.i_row_pos.ensure((size_t)cap * 4);
-        w.i_desc.ensure((size_t)cap * sizeof(int4));
-        w.rows_cap = cap;
-    }
-    // Profile mode, decode chain.  A HIP-event pair around ONE 5-12 us launch adds 2-5 us to what it measures (the pair serialises
-    // the launch processing), so the per-kernel numbers of the bench line come from REPLAY BATCHES instead: after every
-    // profile_every_-th decode step the step's own launches are issued once more, kind by kind -- the QKV GEMM of every layer back
-    // to back between one event pair, then every layer's attention, proj, FC, proj2, then the head -- on the step's real operands
-    // (each layer's weights, the live rows, the real contexts) with the OUTPUTS redirected to scratch buffers (the residual
-    // stream, K/V pages and latents of the sequences are not touched).  One pair per n_layer launches: the interval is the
-    // launch-to-launch period a kernel-trace reports per kernel.  Algorithmic bytes of a GEMM launch: weights once + the activation
-    // rows once + the output tile once (the residual epilogue reads and writes it).
-    ProfEvent& prof_event(int kind, double flops, double bytes, int count) {
-        ProfEvent& ev = next_event(gemm_events_, n_gemm_events_);
-        ev.kind = kind;
-        ev.flops = flops;
-        ev.bytes = bytes;
-        ev.count = count;
-        return ev;
-    }
-    static double gemm_alg_bytes(const GemmRowsArgs& a, GemmRowsEpi epi) {
-        return (a.prec == 2 ? 2.0 : 4.0) * a.K * a.N + 4.0 * ((double)a.M * a.K + (double)a.M * a.N * (epi == kEpiResidual ? 2.0 : 1.0));
-    }
-    // the four GEMM launches of layer l exactly as forward_decode issues them; `redirect` sends every output to the profile scratch
-    GemmRowsArgs decode_gemm_args(RowWs& w, int l, int kind, int M, bool redirect) {
-        const Linear& L = layers_[l].lin[kind];
-        const int mtt = w.rows_cap / 16;   // h, att, act are packed rows (pk_off) with this many 16-row tiles
-        float* h = w.h.as<float>();
-        GemmRowsArgs a{};
-        a.M = M; a.prec = gpt_f16_ ? 2 : gemm_prec_; a.xmt = mtt;
-        a.ksp_buf = ksp_buf_.as<float>(); a.ksp_cnt = ksp_cnt_.as<unsigned>();
-        a.Wt = L.op.Wt; a.N = L.N; a.K = L.K; a.bias = L.op.bias; a.ln_c1 = L.op.c1;
-        if (kind == kQkv) {
-            a.eps = 1e-5f; a.X = h; a.stats_in = w.stats.as<float2>(); a.out = redirect ? prof_q_.as<float>() : w.qbuf.as<float>(); a.ldo = kHidden;
-            a.kv_layer = redirect ? prof_kv_.p : kv_layer(l); a.kv_half = kv_half_ ? 1 : 0; a.row_meta = w.row_meta.as<int>();
-        } else if (kind == kProj) {
-            a.X = w.att.as<float>();
-            a.out = redirect ? prof_h_.as<float>() : h; a.omt = mtt; a.stats_out = redirect ? prof_stats_.as<float2>() : w.stats.as<float2>();
-        } else if (kind == kFc) {
-            a.eps = 1e-5f; a.X = h; a.stats_in = w.stats.as<float2>(); a.out = redirect ? prof_act_.as<float>() : w.act.as<float>(); a.omt = mtt;
-            a.gelu_erf = cfg_.gelu_erf ? 1 : 0;
-        } else {
-            a.X = w.act.as<float>();
-            a.out = redirect ? prof_h_.as<float>() : h; a.omt = mtt;
-            // (ln_f computes its own statistics in final_rows_kernel)
-            if (l + 1 < cfg_.n_layer) a.stats_out = redirect ? prof_stats_.as<float2>() : w.stats.as<float2>();
-        }
-        return a;
-    }
-    static void decode_gemm_kind(int kind, bool* ln, GemmRowsEpi* epi) {
-        *ln = (kind == 0 || kind == 2);
-        *epi = kind == 0 ? kEpiQkv : kind == 2 ? kEpiBiasGelu : kEpiResidual;
-    }
-    // One decode step through the blocks: 5 launches per layer (QKV GEMM with LN1 folded and KV page write, attention,
-    // proj GEMM + residual, FC GEMM with LN2 folded + gelu, proj2 GEMM + residual), no split-K slabs in HBM.  Leaves the
-    // residual stream in w.h (ln_f is applied by final_rows_kernel).
-    void forward_decode(RowWs& w, int M) {
-        const int mtt = w.rows_cap / 16;
-        for (int l = 0; l < cfg_.n_layer; ++l) {
-            for (int kind = 0; kind < 4; ++kind) {
-                bool ln;
-                GemmRowsEpi epi;
-                decode_gemm_kind(kind, &ln, &epi);
-                launch_gemm_rows(decode_gemm_args(w, l, kind, M, false), ln, epi, w.st);
-                if (kind == 0)
-                    launch_paged_attention(w.qbuf.as<float>(), kv_layer(l), w.row_meta.as<int>(), kMaxBlocks, w.att.as<float>(), M, w.st, mtt, kv_half_);
-            }
-        }
-    }
-    GemmRowsArgs head_gemm_args(RowWs& w, int Ms, bool redirect) {
-        GemmRowsArgs a{};
-        a.M = Ms; a.prec = gemm_prec_; a.X = w.ybuf.as<float>(); a.xmt = w.rows_cap / 16; a.Wt = thead_; a.N = kHeadPad; a.K = kHidden; a.bias = headb_;
-        a.out = redirect ? prof_act_.as<float>() : w.P2.as<float>(); a.ldo = kHeadPad;
-        return a;
-    }
-    void profile_replay(RowWs& w, int M) {
-        const int mtt = w.rows_cap / 16, nl = cfg_.n_layer;
-        // (the residual replays READ their output scratch -- out += ... -- so a freshly allocated buffer is defined once)
-        auto scratch = [&](DevBuf& buf, size_t n) {
-            const void* before = buf.p;
-            buf.ensure(n);
-            if (buf.p != before) HIP_CHECK(hipMemsetAsync(buf.p, 0, n, w.st));
-        };
-        scratch(prof_q_, (size_t)w.rows_cap * kHidden * 4);
-        scratch(prof_h_, (size_t)w.rows_cap * kHidden * 4);
-        scratch(prof_stats_, (size_t)w.rows_cap * 64 * sizeof(float2));
-        scratch(prof_act_, (size_t)w.rows_cap * 4 * kHidden * 4);
-        prof_kv_.ensure((size_t)kv_layer_stride_ * (kv_half_ ? 2 : 4));
-        for (int kind = 0; kind < 4; ++kind) {
-            bool ln;
-            GemmRowsEpi epi;
-            decode_gemm_kind(kind, &ln, &epi);
-            const GemmRowsArgs a0 = decode_gemm_args(w, 0, kind, M, true);
-            ProfEvent& ev = prof_event(kind, nl * 2.0 * a0.M * a0.N * a0.K, nl * gemm_alg_bytes(a0, epi), nl);
-            HIP_CHECK(hipEventRecord(ev.a, w.st));
-            for (int l = 0; l < nl; ++l) launch_gemm_rows(decode_gemm_args(w, l, kind, M, true), ln, epi, w.st);
-            HIP_CHECK(hipEventRecord(ev.b, w.st));
-            if (kind == 0) {   // attention of every layer: the step's q rows against each layer's real K/V pages
-                ProfEvent& ea = prof_event(5, nl * 4.0 * kHidden * step_kv_tokens_, nl * ((kv_half_ ? 4.0 : 8.0) * kHidden * step_kv_tokens_ + 8.0 * kHidden * M), nl);
-                HIP_CHECK(hipEventRecord(ea.a, w.st));
-                for (int l = 0; l < nl; ++l)
-                    launch_paged_attention(w.qbuf.as<float>(), kv_layer(l), w.row_meta.as<int>(), kMaxBlocks, prof_h_.as<float>(), M, w.st, mtt, kv_half_);
-                HIP_CHECK(hipEventRecord(ea.b, w.st));
-            }
-        }
-        {   // the mel head has one weight matrix: its replays are L2 / Infinity-Cache warm after the first (1 launch in 152)
-            const GemmRowsArgs a0 = head_gemm_args(w, M, true);
-            ProfEvent& ev = prof_event(4, nl * 2.0 * a0.M * a0.N * a0.K, nl * gemm_alg_bytes(a0, kEpiBias), nl);
-            HIP_CHECK(hipEventRecord(ev.a, w.st));
-            for (int l = 0; l < nl; ++l) launch_gemm_rows(a0, false, kEpiBias, w.st);
-            HIP_CHECK(hipEventRecord(ev.b, w.st));
-        }
-    }
-    // Fixed cost of one HIP-event pair on an otherwise busy stream: recording events between back-to-back short
-    // kernels serialises their launch processing, which inflates a ~12 us kernel by ~3 us.  Measured once as the
-    // median elapsed time of 64 empty pairs and subtracted from every sampled GEMM interval (reported in aur_stats).
-    float event_pair_overhead_ms() {
-        if (event_overhead_ms_ >= 0.f) return event_overhead_ms_;
-        std::vector<hipEvent_t> ev(128);
-        for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-        for (int i = 0; i < 64; ++i) {
-            HIP_CHECK(hipEventRecord(ev[2 * i], st_));
-            HIP_CHECK(hipEventRecord(ev[2 * i + 1], st_));
-        }
-        HIP_CHECK(hipStreamSynchronize(st_));
-        std::vector<float> d(64);
-        for (int i = 0; i < 64; ++i) HIP_CHECK(hipEventElapsedTime(&d[i], ev[2 * i], ev[2 * i + 1]));
-        for (auto& e : ev) (void)hipEventDestroy(e);
-        std::sort(d.begin(), d.end());
-        event_overhead_ms_ = d[32];
-        return event_overhead_ms_;
-    }
-    void collect_gemm_events() {
-        // the replay batches sit behind the step's token read-back on the stream (and, with the pipelined decode, the next step's
-        // batches may already be queued behind them): wait for the last one recorded
-        if (n_gemm_events_) HIP_CHECK(hipEventSynchronize(gemm_events_[n_gemm_events_ - 1].b));
-        const float ovh = n_gemm_events_ ? event_pair_overhead_ms() : 0.f;
-        if (n_gemm_events_) stats_.event_pair_overhead_ms = ovh;
-        for (size_t i = 0; i < n_gemm_events_; ++i) {
-            float ms = 0.f;
-            HIP_CHECK(hipEventElapsedTime(&ms, gemm_events_[i].a, gemm_events_[i].b));
-            const ProfEvent& ev = gemm_events_[i];
-            if (ev.kind == 5) {
-                stats_.attn_ms += ms;
-                stats_.attn_bytes += ev.bytes;
-                stats_.attn_launches += ev.count;
-                continue;
-            }
-            if (ev.kind >= 0 && ev.kind < 5) {
-                stats_.gemm_kind_ms[ev.kind] += ms;
-                stats_.gemm_kind_bytes[ev.kind] += ev.bytes;
-                stats_.gemm_kind_flops[ev.kind] += ev.flops;
-                stats_.gemm_kind_launches[ev.kind] += ev.count;
-            }
-            stats_.gemm_ms_raw += ms;
-            stats_.gemm_ms += std::max(0.f, ms - ovh);   // one pair per batch of ev.count launches
-            stats_.gemm_flops += ev.flops;
-            stats_.gemm_bytes += ev.bytes;
-            stats_.gemm_launches += ev.count;
-        }
-        n_gemm_events_ = 0;
-    }
-    // uploads the query blocks of a batch of prompt rows (prompt_qblocks) for forward_rows and returns their number
-    int upload_qblocks(RowWs& w, const std::vector<int>& row_slot, const std::vector<int>& row_pos) {
-        w.h_qblk = prompt_qblocks(row_slot, row_pos);
-        w.i_qblk.ensure(w.h_qblk.size() * sizeof(int2));
-        HIP_CHECK(hipMemcpyAsync(w.i_qblk.p, w.h_qblk.data(), w.h_qblk.size() * sizeof(int2), hipMemcpyHostToDevice, w.st));
-        return (int)w.h_qblk.size();
-    }
-    // Prompt rows (prefill, speaker prefix, literal second pass): explicit row positions, LDS-tiled GEMMs in the configured arithmetic
-    // (gemm_prec_: bf16 x 3 split by default, exact-f32 MFMA under aur_config.gemm_f32_exact; k ascending for every M => a prompt's rows do not depend on what else was admitted), separate LayerNorm launches.
-    void forward_rows(RowWs& w, int M, const int* d_row_slot, const int* d_row_pos, int n_qblk) {
-        float* h = w.h.as<float>();
-        float* xn = w.xn.as<float>();
-        float* P = w.P.as<float>();
-        const int* bt = block_tables_.as<int>();
-        const int* kvpos = slot_kvpos_.as<int>();
-        AUR_REQUIRE(d_row_pos != nullptr, "forward_rows: prompt rows carry explicit positions");
-        // P = X @ (one linear of the layer), or what `epi` makes of it
-        auto gemm = [&](const float* X, const Linear& L, const GemmGelu* epi, int slabs) {
-            launch_gemm_tile(X, L.K, L.w, P, M, L.N, L.K, w.st, epi, gemm_prec_, slabs, L.split);
-        };
-        launch_rows_ln(nullptr, 0, nullptr, h, layers_[0].lin[kQkv].lnw, layers_[0].lin[kQkv].lnb, xn, M, 1e-5f, w.st);
-        for (int l = 0; l < cfg_.n_layer; ++l) {
-            const Linear* L = layers_[l].lin;
-            void* kvl = kv_layer(l);
-            if (gemm_prec_ == 1) {   // bias, q rows and the K / V page writes in the GEMM's epilogue (27.50 vs 27.62 ms per prefill)
-                GemmGelu qe{L[kQkv].b, nullptr, 0};
-                qe.qbuf = w.qbuf.as<float>(); qe.kv_layer = kvl; qe.row_slot = d_row_slot; qe.row_pos = d_row_pos; qe.block_tables = bt;
-                qe.max_blocks = kMaxBlocks; qe.kv_half = kv_half_ ? 1 : 0;
-                gemm(xn, L[kQkv], &qe, 1);
-            } else {
-                gemm(xn, L[kQkv], nullptr, 1);
-                launch_qkv_epilogue(P, 1, L[kQkv].b, w.qbuf.as<float>(), kvl, d_row_slot, d_row_pos, kvpos, bt, kMaxBlocks, M, w.st, kv_half_);
-            }
-            launch_prompt_attention(w.qbuf.as<float>(), kvl, w.i_qblk.as<int2>(), n_qblk, d_row_slot, d_row_pos, bt, kMaxBlocks, w.att.as<float>(), w.st, kv_half_);
-            // (two K-slabs for this GEMM -- 576 workgroups instead of 288 on 256 CUs: 27.55-27.68 vs 27.82 ms per prefill, four slabs
-            // 27.83-27.93: not worth another slab sum)
-            gemm(w.att.as<float>(), L[kProj], nullptr, 1);
-            launch_rows_ln(P, 1, L[kProj].b, h, L[kFc].lnw, L[kFc].lnb, xn, M, 1e-5f, w.st);
-            const GemmGelu ge{L[kFc].b, w.act.as<float>(), cfg_.gelu_erf ? 1 : 0};
-            gemm(xn, L[kFc], &ge, 1);
-            // K = 4096 against N = 1024: four K-slabs (4x the workgroups of a GEMM that otherwise fills one round of CUs with
-            // 256 dependent k-steps); rows_ln sums them in a fixed order
-            gemm(w.act.as<float>(), L[kProj2], nullptr, kProj2Slabs);
-            const bool last = (l + 1 == cfg_.n_layer);
-            launch_rows_ln(P, kProj2Slabs, L[kProj2].b, h, last ? lnfw_ : layers_[l + 1].lin[kQkv].lnw, last ? lnfb_ : layers_[l + 1].lin[kQkv].lnb,
-                           xn, M, 1e-5f, w.st);
-        }
-    }
-    SamplerArgs sampler_args(RowWs& w, const float* P, int S, int Ms, int Npad, const float* bias, const int* next_kvpos) {
-        SamplerArgs a{};
-        a.P = P; a.S = S; a.Ms = Ms; a.Npad = Npad; a.V = kMelVocab; a.bias = bias;
-        a.sample_slot = w.i_sample_slot.as<int>();
-        a.next_kvpos = next_kvpos;
-        a.seen = seen_.as<unsigned char>();
-        a.slot_tok = slot_tok_.as<int>(); a.slot_pos = slot_pos_.as<int>(); a.slot_kvpos = slot_kvpos_.as<int>();
-        a.slot_ngen = slot_ngen_.as<int>(); a.slot_finished = slot_finished_.as<int>();
-        a.temperature = temperature_.as<float>(); a.top_p = top_p_.as<float>(); a.top_k = top_k_.as<int>();
-        a.rep_penalty = rep_.as<float>(); a.max_tokens = max_tokens_.as<int>(); a.ignore_stop = ignore_stop_.as<int>();
-        a.seed = seed_.as<unsigned>();
-        a.out_tok = w.i_out_tok.as<int>();
-        a.dbg_logits = dbg_capture_ ? dbg_logits_.as<float>() : nullptr;
-        a.stop_token = kStopToken;
-        a.force_full_sort = sampler_full_sort_ ? 1 : 0;
-        return a;
-    }
-    // final_norm -> latent stash -> mel_head GEMM -> fused sampler, in three parts so that the kernel part can be
-    // captured in a hipGraph: (1) host->device index uploads, (2) kernels only, (3) token / finished-flag read-back.
-    void sample_upload(RowWs& w, const std::vector<int>& sample_row, const std::vector<int>& sample_slot,
-                       const std::vector<int>* next_kvpos) {
-        const int Ms = (int)sample_slot.size();
-        w.pin.ensure(((size_t)cfg_.max_seqs * 2 + 16) * sizeof(int));
-        w.i_sample_row.ensure((size_t)std::max(Ms, 64) * 4);
-        w.i_sample_slot.ensure((size_t)std::max(Ms, 64) * 4);
-        w.i_next_kvpos.ensure((size_t)std::max(Ms, 64) * 4);
-        w.i_out_tok.ensure((size_t)std::max(Ms, 64) * 4);
-        w.ybuf.ensure((size_t)std::max(Ms, 64) * kHidden * 4);
-        w.P2.ensure((size_t)std::max(Ms, 64) * kHeadPad * 4);
-        HIP_CHECK(hipMemcpyAsync(w.i_sample_row.p, sample_row.data(), (size_t)Ms * 4, hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_sample_slot.p, sample_slot.data(), (size_t)Ms * 4, hipMemcpyHostToDevice, w.st));
-        if (next_kvpos)
-            HIP_CHECK(hipMemcpyAsync(w.i_next_kvpos.p, next_kvpos->data(), (size_t)Ms * 4, hipMemcpyHostToDevice, w.st));
-    }
-    void sample_kernels(RowWs& w, int Ms, bool has_next_kvpos) {
-        launch_final_norm(w.xn.as<float>(), w.i_sample_row.as<int>(), w.i_sample_slot.as<int>(), fnw_, fnb_, w.ybuf.as<float>(),
-                          latents_.as<float>(), (long)kMaxLatRows * kHidden, slot_ngen_.as<int>(), kMaxLatRows, Ms, 1e-5f, w.st);
-        launch_gemm_tile(w.ybuf.as<float>(), kHidden, headT_, w.P2.as<float>(), Ms, kHeadPad, kHidden, w.st, nullptr, gemm_prec_);
-        SamplerArgs a = sampler_args(w, w.P2.as<float>(), 1, Ms, kHeadPad, headb_, has_next_kvpos ? w.i_next_kvpos.as<int>() : nullptr);
-        launch_sampler(a, w.st);
-    }
-    // decode tail of the gemm_rows chain: rows are the live sequences in order (sample_row = identity), w.h holds the
-    // residual stream: ln_f + final_norm (+ second final_norm into the latent stash) -> mel_head GEMM (+ bias) -> sampler
-    void sample_kernels_decode(RowWs& w, int Ms) {
-        const int mtt = w.rows_cap / 16;
-        launch_final_rows(w.h.as<float>(), mtt, w.i_sample_slot.as<int>(), lnfw_, lnfb_, fnw_, fnb_, w.ybuf.as<float>(),
-                          latents_.as<float>(), (long)kMaxLatRows * kHidden, slot_ngen_.as<int>(), kMaxLatRows, Ms, 1e-5f, w.st);
-        launch_gemm_rows(head_gemm_args(w, Ms, false), false, kEpiBias, w.st);
-        SamplerArgs sa = sampler_args(w, w.P2.as<float>(), 1, Ms, kHeadPad, zero_bias_.as<float>(), nullptr);
-        launch_sampler(sa, w.st);
-    }
-    void sample_readback(RowWs& w, int Ms, hipStream_t st, int* pin = nullptr) {
-        if (!pin) pin = w.pin.as<int>();
-        HIP_CHECK(hipMemcpyAsync(pin, w.i_out_tok.p, (size_t)Ms * 4, hipMemcpyDeviceToHost, st));   // token | finished bit
-    }
-    void sample_launch(RowWs& w, const std::vector<int>& sample_row, const std::vector<int>& sample_slot,
-                       const std::vector<int>* next_kvpos) {
-        sample_upload(w, sample_row, sample_slot, next_kvpos);
-        sample_kernels(w, (int)sample_slot.size(), next_kvpos != nullptr);
-        sample_readback(w, (int)sample_slot.size(), w.st);
-    }
-    // after the stream has been synchronised: append tokens, retire finished sequences
-    void sample_collect(RowWs& w, const std::vector<int>& sample_slot) {
-        const int Ms = (int)sample_slot.size();
-        const int* pin = w.pin.as<int>();
-        for (int j = 0; j < Ms; ++j) {
-            Seq* s = slot_owner_[sample_slot[j]];
-            s->tokens.push_back(pin[j] & ~kTokFinishedBit);
+    // the read-back of a sampler launch, once its copy has landed: appends the tokens (token | finished bit per row of `slots`),
+    // notes the sequences that finished with theirs, returns the rows that drew one
+    int append_tokens(const int* pin, const std::vector<int>& slots) {
+        int rows = 0;
+        for (size_t j = 0; j < slots.size(); ++j) {
+            const int raw = pin[j];
+            if (raw < 0) continue;   // ghost row of a sequence that had already finished
+            Seq* s = slot_owner_[slots[j]];
+            AUR_REQUIRE(s && s->state == SeqState::RUNNING, "token read-back for a slot without a running sequence");
+            s->tokens.push_back(raw & ~kTokFinishedBit);
             s->n_gen.fetch_add(1, std::memory_order_relaxed);
             stats_.tokens_generated++;
-            if (pin[j] & kTokFinishedBit) just_finished_.push_back(s);
+            ++rows;
+            if (raw & kTokFinishedBit) just_finished_.push_back(s);
         }
+        return rows;
     }
     // sequences whose tokens completed in this step: (optional literal second pass) -> latent pool -> vocoder queue
     void retire_finished() {
@@ -1406,8 +900,6 @@ private:
     // n_cond .. n_cond+N-1 (i.e. drop the last 5), apply final_norm twice.  The sequence still owns its slot and KV
     // blocks, which are simply overwritten.  The default path (latent stash) never runs this.
     void second_pass(const std::vector<Seq*>& seqs) {
-        RowWs& w = ws_[0];
-        last_active_.clear();
         std::vector<int4> desc;
         std::vector<int> row_slot, row_pos, lat_row0;
         for (Seq* s : seqs) {
@@ -1427,22 +919,15 @@ private:
             }
         }
         const int M = (int)row_slot.size();
-        ensure_rows(w, M);
-        HIP_CHECK(hipMemcpyAsync(w.i_desc.p, desc.data(), (size_t)M * sizeof(int4), hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_row_slot.p, row_slot.data(), (size_t)M * 4, hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_row_pos.p, row_pos.data(), (size_t)M * 4, hipMemcpyHostToDevice, w.st));
-        launch_embed_prompt(w.i_desc.as<int4>(), spk_table_.as<float>(), text_emb_, text_pos_, wte_, wpe_, w.h.as<float>(), M, w.st);
-        forward_rows(w, M, w.i_row_slot.as<int>(), w.i_row_pos.as<int>(), upload_qblocks(w, row_slot, row_pos));
+        gpt_->prompt_rows(desc, row_slot, row_pos, spk_table_.as<float>());
         for (size_t k = 0; k < seqs.size(); ++k) {
             Seq* s = seqs[k];
             if (latpool_free_.empty()) throw StateError("latent pool exhausted");
             s->pool_idx = latpool_free_.back();
             latpool_free_.pop_back();
-            launch_double_norm_rows(w.xn.as<float>() + (long)lat_row0[k] * kHidden,
-                                    latpool_.as<float>() + (long)s->pool_idx * kMaxLatRows * kHidden, (int)s->tokens.size(),
-                                    fnw_, fnb_, 1e-5f, w.st);
+            gpt_->double_norm_rows(lat_row0[k], latpool_.as<float>() + (long)s->pool_idx * kMaxLatRows * kHidden, (int)s->tokens.size());
         }
-        HIP_CHECK(hipStreamSynchronize(w.st));
+        HIP_CHECK(hipStreamSynchronize(st_));
         stats_.prefill_rows += M;
     }
     void finish_tokens(Seq* s) {
@@ -1463,7 +948,7 @@ private:
             latpool_free_.pop_back();
             const size_t n = s->tokens.size() * (size_t)kHidden * sizeof(float);
             HIP_CHECK(hipMemcpyAsync(latpool_.as<float>() + (long)s->pool_idx * kMaxLatRows * kHidden,
-                                     latents_.as<float>() + (long)s->slot * kMaxLatRows * kHidden, n, hipMemcpyDeviceToDevice, st_));
+                                     gpt_->stash(s->slot), n, hipMemcpyDeviceToDevice, st_));
         }
         HIP_CHECK(hipEventRecord(ev_lat_, st_));
         std::lock_guard<std::mutex> lk(mu_);
@@ -1474,20 +959,7 @@ private:
         s->slot = -1;
         voc_queue_.push_back(s);
     }
-    void init_slots(const std::vector<SlotInit>& init) {
-        i_init_.ensure(init.size() * sizeof(SlotInit));
-        HIP_CHECK(hipMemcpyAsync(i_init_.p, init.data(), init.size() * sizeof(SlotInit), hipMemcpyHostToDevice, st_));
-        trace_launch("init_slots_kernel");
-        hipLaunchKernelGGL(init_slots_kernel, dim3((unsigned)init.size()), dim3(256), 0, st_, i_init_.as<SlotInit>(),
-                           slot_tok_.as<int>(), slot_pos_.as<int>(), slot_kvpos_.as<int>(), slot_ngen_.as<int>(),
-                           slot_finished_.as<int>(), temperature_.as<float>(), top_p_.as<float>(), top_k_.as<int>(),
-                           rep_.as<float>(), max_tokens_.as<int>(), ignore_stop_.as<int>(), seed_.as<unsigned>(),
-                           seen_.as<unsigned char>(), kStartToken);
-        HIP_CHECK(hipGetLastError());
-    }
     void prefill(const std::vector<Seq*>& seqs) {
-        RowWs& w = ws_[0];
-        last_active_.clear();   // prefill reuses the index buffers of the decode chain
         std::vector<int4> desc;
         std::vector<int> row_slot, row_pos, sample_row, sample_slot, next_kvpos;
         std::vector<SlotInit> init;
@@ -1499,7 +971,7 @@ private:
             for (int i = first; i < 32; ++i) desc.push_back(make_int4(0, i, s->spk_row, 0));
             for (int i = 0; i < (int)s->text_ids.size(); ++i) {
                 const int id = s->text_ids[i];
-                AUR_REQUIRE(id >= 0 && id < text_vocab_ && i < text_positions_, "text id / position out of range");
+                AUR_REQUIRE(gpt_->text_ok(id, i), "text id / position out of range");
                 desc.push_back(make_int4(1, id, i, 0));
             }
             desc.push_back(make_int4(2, kStartToken, 0, 0));
@@ -1512,37 +984,15 @@ private:
             next_kvpos.push_back(s->n_prompt);
         }
         const int M = (int)row_slot.size();
-        ensure_rows(w, M);
-        init_slots(init);
-        HIP_CHECK(hipMemcpyAsync(block_tables_.p, h_block_tables_.data(), h_block_tables_.size() * 4, hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_desc.p, desc.data(), (size_t)M * sizeof(int4), hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_row_slot.p, row_slot.data(), (size_t)M * 4, hipMemcpyHostToDevice, w.st));
-        HIP_CHECK(hipMemcpyAsync(w.i_row_pos.p, row_pos.data(), (size_t)M * 4, hipMemcpyHostToDevice, w.st));
-        if (debug_sync())
-            fprintf(stderr, "[aur] prefill M=%d desc=%p spk=%p temb=%p tpos=%p wte=%p wpe=%p h=%p d0=(%d,%d,%d) dl=(%d,%d,%d)\n", M,
-                    w.i_desc.p, spk_table_.p, (const void*)text_emb_, (const void*)text_pos_, (const void*)wte_, (const void*)wpe_, w.h.p,
-                    desc[0].x, desc[0].y, desc[0].z, desc[M - 1].x, desc[M - 1].y, desc[M - 1].z);
-        launch_embed_prompt(w.i_desc.as<int4>(), spk_table_.as<float>(), text_emb_, text_pos_, wte_, wpe_, w.h.as<float>(), M, w.st);
-        forward_rows(w, M, w.i_row_slot.as<int>(), w.i_row_pos.as<int>(), upload_qblocks(w, row_slot, row_pos));
-        if (dbg_capture_) {
-            dbg_lnf_.ensure((size_t)M * kHidden * 4);
-            HIP_CHECK(hipMemcpyAsync(dbg_lnf_.p, w.xn.p, (size_t)M * kHidden * 4, hipMemcpyDeviceToDevice, w.st));
-        }
+        gpt_->init_slots(init);
+        gpt_->upload_block_tables(h_block_tables_);
+        gpt_->prompt_rows(desc, row_slot, row_pos, spk_table_.as<float>());
+        gpt_->capture_prompt_rows(M);   // (aur_dbg_prefill)
         stats_.prefill_rows += M;
-        sample_launch(w, sample_row, sample_slot, &next_kvpos);
-        HIP_CHECK(hipStreamSynchronize(w.st));
-        sample_collect(w, sample_slot);
+        const int* pin = gpt_->sample_prompt(sample_row, sample_slot, next_kvpos);
+        HIP_CHECK(hipStreamSynchronize(st_));
+        append_tokens(pin, sample_slot);
         retire_finished();
-    }
-    // One decode step: embed -> 30 x (QKV GEMM, attention, proj, FC, proj2) -> final norms -> head GEMM -> sampler, 154
-    // launches that depend only on device-resident state (hipGraph replay of the chain was measured within noise in round 2:
-    // the launches are already back to back).
-    void decode_kernels(RowWs& w, int Mk) {
-        launch_embed_decode(w.i_row_slot.as<int>(), slot_tok_.as<int>(), slot_pos_.as<int>(), wte_, wpe_, w.h.as<float>(), Mk, w.st,
-                            w.rows_cap / 16, w.stats.as<float2>(), w.row_meta.as<int>(), slot_kvpos_.as<int>(),
-                            block_tables_.as<int>(), kMaxBlocks);
-        forward_decode(w, Mk);
-        sample_kernels_decode(w, Mk);
     }
     // ---- pipelined decode (default): the step's kernel chain depends only on device-resident state, so step s+1 is
     // enqueued BEFORE the host waits for the token / finished-flag read-back of step s (otherwise the GPU idles for the
@@ -1556,17 +1006,6 @@ private:
         bool profiled = false;
     };
     InFlight launch_decode_step(const std::vector<int>& active) {
-        RowWs& w = ws_[0];
-        const int M = (int)active.size();
-        if (active != last_active_) {
-            w.sample_slot = active;
-            w.sample_row.resize(M);
-            for (int i = 0; i < M; ++i) w.sample_row[i] = i;
-            ensure_rows(w, M);
-            HIP_CHECK(hipMemcpyAsync(w.i_row_slot.p, w.sample_slot.data(), (size_t)M * 4, hipMemcpyHostToDevice, st_));
-            sample_upload(w, w.sample_row, w.sample_slot, nullptr);
-            HIP_CHECK(hipStreamSynchronize(st_));   // pageable sources: the vectors may change before the copies run
-        }
         InFlight f;
         f.on = true;
         f.slots = active;
@@ -1576,47 +1015,26 @@ private:
         pin_rb_[f.buf].ensure(((size_t)cfg_.max_seqs * 2 + 16) * sizeof(int));
         // algorithmic bytes of this step: every live sequence's context (prompt + tokens so far, + 1 if the previous step is
         // still in flight) in K and V, all layers; the weights once
-        step_kv_tokens_ = 0.0;
+        double kv_tokens = 0.0;
         for (int slot : active) {
             const Seq* sq = slot_owner_[slot];
-            step_kv_tokens_ += (double)(sq->n_prompt + (int)sq->tokens.size() + (infl_.on ? 1 : 0));
+            kv_tokens += (double)(sq->n_prompt + (int)sq->tokens.size() + (infl_.on ? 1 : 0));
         }
-        stats_.decode_kv_bytes += (kv_half_ ? 4.0 : 8.0) * kHidden * step_kv_tokens_ * cfg_.n_layer;
-        stats_.decode_weight_bytes += (gpt_f16_ ? 2.0 : 4.0) * cfg_.n_layer * 12.0 * kHidden * kHidden + 4.0 * kHidden * kMelVocab;
-        HIP_CHECK(hipEventRecord(ev_ds_[f.buf], st_));
-        decode_kernels(w, M);
-        HIP_CHECK(hipEventRecord(ev_de_[f.buf], st_));
-        // (the sampler writing the tokens straight into the pinned block instead of this 256-byte copy: 621.3 vs 621.8 ms per bench
-        // step, 1.193 vs 1.194 ms per single-utterance decode step -- the copy is not on the critical path of the pipelined loop)
-        sample_readback(w, M, st_, pin_rb_[f.buf].as<int>());
-        HIP_CHECK(hipEventRecord(ev_rb_[f.buf], st_));
-        if (f.profiled) profile_replay(w, M);   // behind the read-back: the step's tokens do not wait for it
-        last_active_ = active;
+        stats_.decode_kv_bytes += (cfg_.kv_fp16 ? 4.0 : 8.0) * kHidden * kv_tokens * cfg_.n_layer;
+        stats_.decode_weight_bytes += (cfg_.gpt_fp16 ? 2.0 : 4.0) * cfg_.n_layer * 12.0 * kHidden * kHidden + 4.0 * kHidden * kMelVocab;
+        gpt_->decode_step(active, f.profiled, kv_tokens, pin_rb_[f.buf].as<int>(), ev_step_[f.buf]);
         return f;
     }
     void collect_decode_step(InFlight& f) {
-        HIP_CHECK(hipEventSynchronize(ev_rb_[f.buf]));
-        const int* pin = pin_rb_[f.buf].as<int>();
-        int rows = 0;
-        for (size_t j = 0; j < f.slots.size(); ++j) {
-            const int raw = pin[j];
-            if (raw < 0) continue;   // ghost row of a sequence that had already finished
-            const int tok = raw & ~kTokFinishedBit;
-            Seq* s = slot_owner_[f.slots[j]];
-            AUR_REQUIRE(s && s->state == SeqState::RUNNING, "decode read-back for a slot without a running sequence");
-            s->tokens.push_back(tok);
-            s->n_gen.fetch_add(1, std::memory_order_relaxed);
-            stats_.tokens_generated++;
-            ++rows;
-            if (raw & kTokFinishedBit) just_finished_.push_back(s);
-        }
+        HIP_CHECK(hipEventSynchronize(ev_step_[f.buf].readback));
+        const int rows = append_tokens(pin_rb_[f.buf].as<int>(), f.slots);
         float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, ev_ds_[f.buf], ev_de_[f.buf]));
+        HIP_CHECK(hipEventElapsedTime(&ms, ev_step_[f.buf].start, ev_step_[f.buf].end));
         stats_.gpt_ms += ms;
         stats_.decode_ms += ms;
         stats_.decode_steps++;
         stats_.decode_rows += rows;
-        if (f.profiled) collect_gemm_events();
+        if (f.profiled) gpt_->collect_profile(stats_);
         f.on = false;
     }
     // launch the next step ahead of the read-back only if some sequence is certain to need it
@@ -1764,31 +1182,16 @@ private:
     int device_;
     hipStream_t st_ = nullptr;
     hipEvent_t ev_a_ = nullptr, ev_b_ = nullptr;
-    std::unordered_map<std::string, Tensor> w_;
-    bool gpt_ready_ = false;
-    std::vector<LayerW> layers_;
-    std::vector<std::unique_ptr<DevBuf>> packed_;   // pack_wt16 copies (decode GEMM layout)
-    DevBuf fold_scratch_;                           // load-time scratch of launch_fold_ln
-    int gemm_prec_ = 1;                             // GemmRowsArgs.prec of every decode GEMM (aur_config.gemm_f32_exact)
-    bool gpt_f16_ = false;                          // aur_config.gpt_fp16: the four per-layer decode GEMMs run with prec 2 on fp16 copies
-    const float* thead_ = nullptr;
+    WeightTable w_;                     // what aur_load_weights has loaded; the three networks bind out of it
+    std::unique_ptr<GptNet> gpt_;       // the GPT: layer tables, K/V pool, per-slot device state, forward chains, sampler, decode profile (gpt_net.h)
     int fail_at_step_ = 0;              // AUR_TEST_FAIL_STEP=n: throw inside the n-th aur_step (recovery test)
     int fail_at_voc_ = 0;               // AUR_TEST_FAIL_VOC=n: throw inside the n-th vocoder launch, after the batch left the queue
     bool voc_block_held_ = false;       // the vocoder batch holds a reference on voc_block_
-    const float *wte_ = nullptr, *wpe_ = nullptr, *lnfw_ = nullptr, *lnfb_ = nullptr, *fnw_ = nullptr, *fnb_ = nullptr,
-                *headT_ = nullptr, *headb_ = nullptr, *text_emb_ = nullptr, *text_pos_ = nullptr;
-    int text_vocab_ = 0, text_positions_ = 0;
-    // KV pool
-    DevBuf kv_;
-    long n_blocks_ = 0, kv_layer_stride_ = 0;   // stride in elements
-    bool kv_half_ = false;                        // aur_config.kv_fp16
-    void* kv_layer(int l) const { return (char*)kv_.p + (size_t)l * kv_layer_stride_ * (kv_half_ ? 2 : 4); }
+    // K/V block allocator (the pool itself is GptNet's)
+    long n_blocks_ = 0;
     std::vector<int> free_blocks_;
     std::vector<int> h_block_tables_;
-    // per-slot device state
-    DevBuf slot_tok_, slot_pos_, slot_kvpos_, slot_ngen_, slot_finished_, temperature_, top_p_, top_k_, rep_, max_tokens_,
-        ignore_stop_, seed_, block_tables_, seen_, latents_;
-    DevBuf spk_table_, spk_emb_, voc_cond_, zero_bias_;
+    DevBuf spk_table_, spk_emb_, voc_cond_;
     std::map<uint64_t, int> spk_rows_;
     struct SpeakerInfo {
         int blocks[2] = {-1, -1};
@@ -1804,8 +1207,6 @@ private:
     void* comm_ = nullptr;   // ncclComm_t
     int comm_rank_ = 0, comm_world_ = 1;
     DevBuf bcast_buf_;
-    // row workspace
-    RowWs ws_[2];
     // vocoder stage
     hipStream_t st_voc_ = nullptr;
     hipEvent_t ev_lat_ = nullptr, ev_voc_done_ = nullptr;
@@ -1822,29 +1223,16 @@ private:
     std::vector<std::unique_ptr<PinBlock>> result_blocks_;   // pool; a block is free when refs == 0 (guarded by mu_)
     PinBlock* voc_block_ = nullptr;                          // block of the in-flight vocoder batch
     InFlight infl_;                     // decode step launched but not yet collected
-    PinBuf pin_rb_[2];
-    hipEvent_t ev_rb_[2] = {nullptr, nullptr}, ev_ds_[2] = {nullptr, nullptr}, ev_de_[2] = {nullptr, nullptr};
+    PinBuf pin_rb_[2];                  // token read-backs of the two steps that can be in flight, and their events
+    StepEvents ev_step_[2];
     int rb_next_ = 0;
-    bool sampler_full_sort_ = false;    // AUR_SAMPLER_FULL_SORT=1: disable the sampler's top-k fast path (A/B)
     bool host_trace_ = false;           // AUR_HOST_TRACE=1: host time of enqueueing a decode step vs waiting for the previous one (stderr, every 256 steps)
     long ht_launch_ns_ = 0, ht_wait_ns_ = 0, ht_n_ = 0;
     bool pipeline_ = true;              // AUR_DECODE_PIPELINE=0: wait for every read-back before launching the next step
-    std::vector<int> last_active_;      // live slots whose row indices are resident in the decode chain's index buffers
-    hipStream_t st2_ = nullptr;
-    DevBuf i_init_;
-    DevBuf dbg_lnf_, dbg_logits_;
-    bool dbg_capture_ = false;
     std::unique_ptr<HifiGan> voc_;      // the vocoder's forward graph, weights tables, workspace and profile events (voc_net.h)
     DevBuf tmp_lat_, tmp_wav_;          // vocode_host's device copies
-    std::vector<ProfEvent> gemm_events_;
-    size_t n_gemm_events_ = 0;
     int profile_every_ = kProfileEvery;
-    DevBuf prof_q_, prof_h_, prof_stats_, prof_act_, prof_kv_;   // output scratch of profile_replay
-    DevBuf ksp_buf_, ksp_cnt_;   // GemmRowsArgs::ksp_buf / ksp_cnt
-    bool gemm_presplit_ = true;  // prompt-row GEMMs read their weights as the three bf16 planes packed at load time (launch_pack_wsplit)
-    double step_kv_tokens_ = 0.0;       // sum of context lengths of the step being launched (profile accounting)
     long decode_step_count_ = 0;
-    float event_overhead_ms_ = -1.f;
     // sequences
     std::mutex mu_;
     uint64_t next_id_ = 1;

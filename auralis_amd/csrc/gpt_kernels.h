@@ -227,4 +227,14 @@ struct SamplerArgs {
 void launch_sampler(const SamplerArgs& a, hipStream_t st);
 constexpr int kSeenStride = 1040;
 
+// the per-slot state of SamplerArgs at admission: slot_tok = start_token, positions 0, the request's sampling parameters, and a
+// seen row that holds only token 1 and the start token
+struct SlotInit {
+    int slot; float temperature, top_p; int top_k; float rep_penalty; int max_tokens, ignore_stop; unsigned seed;
+    int ngen;   // initial n_gen (0; dbg_sample injects a step)
+};
+void launch_init_slots(const SlotInit* init, int n, int* slot_tok, int* slot_pos, int* slot_kvpos, int* slot_ngen, int* slot_finished,
+                       float* temperature, float* top_p, int* top_k, float* rep, int* max_tokens, int* ignore_stop, unsigned* seed,
+                       unsigned char* seen, int start_token, hipStream_t st);
+
 }  // namespace aur

@@ -1816,4 +1816,35 @@ void launch_sampler(const SamplerArgs& a, hipStream_t st) {
     HIP_CHECK(hipGetLastError());
 }
 
+__global__ __launch_bounds__(256) void init_slots_kernel(const SlotInit* __restrict__ init, int* slot_tok, int* slot_pos, int* slot_kvpos,
+                                                         int* slot_ngen, int* slot_finished, float* temperature, float* top_p, int* top_k,
+                                                         float* rep, int* max_tokens, int* ignore_stop, unsigned* seed, unsigned char* seen,
+                                                         int start_token) {
+    const SlotInit s = init[blockIdx.x];
+    unsigned char* row = seen + (long)s.slot * kSeenStride;
+    for (int i = threadIdx.x; i < kSeenStride; i += 256) row[i] = (i == 1 || i == start_token) ? 1 : 0;
+    if (threadIdx.x == 0) {
+        slot_tok[s.slot] = start_token;
+        slot_pos[s.slot] = 0;
+        slot_kvpos[s.slot] = 0;
+        slot_ngen[s.slot] = s.ngen;
+        slot_finished[s.slot] = 0;
+        temperature[s.slot] = s.temperature;
+        top_p[s.slot] = s.top_p;
+        top_k[s.slot] = s.top_k;
+        rep[s.slot] = s.rep_penalty;
+        max_tokens[s.slot] = s.max_tokens;
+        ignore_stop[s.slot] = s.ignore_stop;
+        seed[s.slot] = s.seed;
+    }
+}
+void launch_init_slots(const SlotInit* init, int n, int* slot_tok, int* slot_pos, int* slot_kvpos, int* slot_ngen, int* slot_finished,
+                       float* temperature, float* top_p, int* top_k, float* rep, int* max_tokens, int* ignore_stop, unsigned* seed,
+                       unsigned char* seen, int start_token, hipStream_t st) {
+    trace_launch("init_slots_kernel");
+    hipLaunchKernelGGL(init_slots_kernel, dim3((unsigned)n), dim3(256), 0, st, init, slot_tok, slot_pos, slot_kvpos, slot_ngen, slot_finished,
+                       temperature, top_p, top_k, rep, max_tokens, ignore_stop, seed, seen, start_token);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace aur

@@ -4,9 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <cstring>
-#include <functional>
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "../../include/auralis_amd.h"
@@ -96,9 +94,8 @@ inline int out_samples(int n_lat, float speed, int sample_rate) {
 
 class HifiGan {
 public:
-    using WeightFn = std::function<const float*(const std::string&)>;
     // (on the engine's device: the resampler's table, no weight of the checkpoint, goes up here)
-    HifiGan(WeightFn w, hipStream_t st, VocLayout lay) : W_(std::move(w)), st_(st), lay_(lay) { v_rtab_.upload(resample_table()); }
+    HifiGan(WeightTable& w, hipStream_t st, VocLayout lay) : W_(w), st_(st), lay_(lay) { v_rtab_.upload(resample_table()); }
     ~HifiGan() {   // (not copyable: the workspace buffers are not)
         for (auto& e : events_) (void)hipEventDestroy(e.a), (void)hipEventDestroy(e.b);
     }
@@ -107,7 +104,7 @@ public:
     void bind() {
         if (bound_) return;
         auto layer = [&](const std::string& n) {
-            return ConvLayer{W_("voc." + n + ".wp"), W_("voc." + n + ".bias"), lay_.f16 ? W_("voc16." + n + ".wp") : nullptr};
+            return ConvLayer{W_.W("voc." + n + ".wp"), W_.W("voc." + n + ".bias"), lay_.f16 ? W_.W("voc16." + n + ".wp") : nullptr};
         };
         pre_ = layer("conv_pre");
         for (int i = 0; i < 4; ++i) {
@@ -118,7 +115,7 @@ public:
                     c1_[i][j][c] = layer(p + "c1" + n), c2_[i][j][c] = layer(p + "c2" + n);
                 }
         }
-        post_ = W_("voc.conv_post.w");
+        post_ = W_.W("voc.conv_post.w");
         bound_ = true;
     }
     void unbind() { bound_ = false; }
@@ -266,7 +263,7 @@ private:
         HIP_CHECK(hipEventRecord(ev.b, st_));
     }
 
-    WeightFn W_;
+    WeightTable& W_;
     hipStream_t st_;
     VocLayout lay_;
     bool bound_ = false, profile_ = false;

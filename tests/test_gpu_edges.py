@@ -135,6 +135,62 @@ def test_pipelined_decode_equals_synchronous(dims, monkeypatch):
         assert np.array_equal(x["wav"], y["wav"]) and np.array_equal(x["latents"], y["latents"])
 
 
+def _generate_three(e, dims, key):
+    """Three sequences through a 3-slot engine: one greedy, two sampled with fixed seeds, max_tokens 6 / 10 / 12."""
+    sids = []
+    for k, max_tokens in enumerate((6, 10, 12)):
+        ids = make_synthetic_text_ids(dims, n_text=9 + 3 * k, seed=70 + k)
+        sids.append(e.submit(ids, key, temperature=0.9 if k else 0.0, top_k=50, top_p=0.85, max_tokens=max_tokens, seed=300 + k,
+                             ignore_stop=True))
+    outs = {o["seq_id"]: o for o in e.run_until_done()}
+    return [{f: np.array(outs[s][f]) for f in ("tokens", "wav", "latents")} for s in sids]   # copies: the engine reuses its result blocks
+
+
+def _assert_same_outputs(a, b):
+    for x, y, n in zip(a, b, (6, 10, 12)):
+        assert len(x["tokens"]) == n and x["tokens"].tolist() == y["tokens"].tolist()
+        assert np.array_equal(x["wav"], y["wav"]) and np.array_equal(x["latents"], y["latents"])
+
+
+@pytest.mark.parametrize("gpt_fp16", [0, 1])
+def test_second_load_rebinds_the_gpt(dims, gpt_fp16):
+    """A second aur_load_weights on a used engine drops the GPT's layer tables and packed operands, and the next step binds them
+    again.  (1) The same tensors loaded again: tokens, wav and latents of the same requests are bit for bit those of the first run
+    (fp16 weights: the effective matrices are converted again from what was loaded).  (2) Default mode: a subset with one changed
+    matrix, the voice registered under a new key (its shared prefix K/V is computed on the new weights): bit for bit a fresh engine
+    loaded with the full changed set."""
+    from auralis_amd._lib import NativeEngine
+    from tests.gpu_util import packed_weights
+    packed, _, _ = packed_weights(2)
+    cond, spk = make_synthetic_conditioning(dims)
+    e = NativeEngine(n_layer=2, max_seqs=3, gpt_fp16=bool(gpt_fp16))
+    try:
+        e.load_weights(packed)
+        e.set_conditioning(SPK_KEY, cond.numpy(), spk.numpy())
+        first = _generate_three(e, dims, SPK_KEY)
+        e.load_weights(packed)
+        _assert_same_outputs(first, _generate_three(e, dims, SPK_KEY))
+        if gpt_fp16:
+            return
+        name = "gpt.h.1.mlp.c_fc.w"
+        changed = dict(packed)
+        changed[name] = (np.asarray(packed[name], dtype=np.float32) * np.float32(1.01)).astype(np.float32)
+        e.load_weights({name: changed[name]})
+        e.set_conditioning(4343, cond.numpy(), spk.numpy())
+        got = _generate_three(e, dims, 4343)
+    finally:
+        e.close()
+    fresh = NativeEngine(n_layer=2, max_seqs=3)
+    try:
+        fresh.load_weights(changed)
+        fresh.set_conditioning(4343, cond.numpy(), spk.numpy())
+        want = _generate_three(fresh, dims, 4343)
+    finally:
+        fresh.close()
+    _assert_same_outputs(got, want)
+    assert any(x["tokens"].tolist() != y["tokens"].tolist() or not np.array_equal(x["wav"], y["wav"]) for x, y in zip(got, first))
+
+
 def test_failed_step_releases_slots_blocks_and_engine_stays_usable(dims, monkeypatch):
     """A throw inside aur_step (here injected: AUR_TEST_FAIL_STEP) fails the sequences that were in flight (error code in
     their results, no audio), returns their slots / KV blocks / pool entries, keeps queued sequences, and the engine
