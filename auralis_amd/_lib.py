@@ -45,13 +45,15 @@ class aur_seq_desc(C.Structure):
     _fields_ = [("text_ids", C.POINTER(C.c_int32)), ("n_text", C.c_int32), ("speaker_key", C.c_uint64),
                 ("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32),
                 ("repetition_penalty", C.c_float), ("max_tokens", C.c_int32), ("seed", C.c_uint32),
-                ("ignore_stop", C.c_int32), ("priority", C.c_int32), ("sample_rate", C.c_int32), ("speed", C.c_float)]
+                ("ignore_stop", C.c_int32), ("encoding", C.c_int32), ("priority", C.c_int32), ("sample_rate", C.c_int32),
+                ("speed", C.c_float)]
 
 
 class aur_result(C.Structure):
     _fields_ = [("seq_id", C.c_uint64), ("n_tokens", C.c_int32), ("tokens", C.POINTER(C.c_int32)),
                 ("n_samples", C.c_int32), ("wav", C.POINTER(C.c_float)), ("n_latent_rows", C.c_int32),
-                ("latents", C.POINTER(C.c_float)), ("error", C.c_int32), ("sample_rate", C.c_int32)]
+                ("latents", C.POINTER(C.c_float)), ("error", C.c_int32), ("enc", C.POINTER(C.c_uint8)),
+                ("n_enc", C.c_int64), ("sample_rate", C.c_int32)]
 
 
 class aur_stats(C.Structure):
@@ -94,6 +96,7 @@ EXPORTS = [
     "aur_dbg_paged_attention", "aur_dbg_prompt_attention", "aur_dbg_layernorm", "aur_dbg_conv1d", "aur_dbg_conv1d_f16", "aur_dbg_prefill", "aur_dbg_sample",
     "aur_dbg_conv1d_args", "aur_dbg_resblock_round_f16", "aur_dbg_interp2", "aur_dbg_interp3", "aur_dbg_conv_post", "aur_dbg_resample_out",
     "aur_dbg_gemm_tile", "aur_dbg_qkv_rows", "aur_dbg_rows_ln",
+    "aur_flac_bound", "aur_encode_flac", "aur_dbg_flac_encode",
 ]
 
 _lib = None
@@ -167,6 +170,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "aur_dbg_interp3": [eng, fp, ip, ip, fp] + [C.c_int32] * 6 + [fp, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_conv_post": [eng, fp, fp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, fp, C.c_float, C.POINTER(C.c_int64)],
         "aur_dbg_resample_out": [eng, fp, ip, ip, C.c_int32, C.c_int32, fp, C.c_int32, C.c_float, C.POINTER(C.c_int64)],
+        "aur_encode_flac": [eng, C.POINTER(fp), ip, ip, C.c_int32, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_int64)],
+        "aur_dbg_flac_encode": [eng, fp, ip, ip, C.c_int32, C.c_int64, C.POINTER(C.c_uint8), C.c_int64, ip],
         "aur_dbg_prefill": [eng, ip, C.c_int32, C.c_uint64, C.c_float, fp, fp],
         "aur_dbg_sample": [eng, fp, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float,
                            C.POINTER(C.c_uint8), C.c_uint32, C.c_int32, ip],
@@ -175,6 +180,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
+    lib.aur_flac_bound.argtypes = [C.c_int64]
+    lib.aur_flac_bound.restype = C.c_int64
     if path is None:
         _lib = lib
     return lib
@@ -194,6 +201,8 @@ def samples_for(n_lat: int, speed: float = 0.0) -> int:
 
 # output sample rates the engine delivers (aur_seq_desc.sample_rate; 0 = unset = 24000)
 OUTPUT_SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+ENCODINGS = {None: 0, "": 0, "flac": 1}   # aur_seq_desc.encoding (AUR_ENC_FLAC16 = 1)
+FLAC_MAX_SAMPLES = 1 << 24                # per stream of aur_encode_flac
 RESAMPLE_TILE = 1024   # output samples one workgroup of resample_out_kernel owns (kResampleTile, csrc/vocoder_kernels.h)
 
 
@@ -390,12 +399,14 @@ class NativeEngine:
     # -- sequences -------------------------------------------------------------------------------------
     def submit(self, text_ids: Sequence[int], speaker_key: int, temperature: float = 0.75, top_p: float = 0.85,
                top_k: int = 50, repetition_penalty: float = 5.0, max_tokens: int = 605, seed: int = 0,
-               ignore_stop: bool = False, priority: int = 0, speed: float = 0.0, sample_rate: int = 0) -> int:
+               ignore_stop: bool = False, priority: int = 0, speed: float = 0.0, sample_rate: int = 0, encoding=None) -> int:
         """`speed`: aur_seq_desc.speed, 0 = unset (= 1.0), else in [0.5, 2.0]; `sample_rate`: aur_seq_desc.sample_rate, 0 = unset
-        (= 24000), else one of OUTPUT_SAMPLE_RATES (anything else: AurError, AUR_E_INVALID)."""
+        (= 24000), else one of OUTPUT_SAMPLE_RATES (anything else: AurError, AUR_E_INVALID); `encoding`: aur_seq_desc.encoding, None / 0
+        or "flac" / AUR_ENC_FLAC16 (the result then carries `encoded`, the 16-bit FLAC stream of `wav`)."""
+        enc = ENCODINGS[encoding] if encoding in ENCODINGS else int(encoding)
         ids = _i32(list(text_ids))
         d = aur_seq_desc(_ip(ids), len(ids), speaker_key, temperature, top_p, top_k, repetition_penalty,
-                         max_tokens, seed & 0xFFFFFFFF, int(ignore_stop), int(priority), int(sample_rate), float(speed))
+                         max_tokens, seed & 0xFFFFFFFF, int(ignore_stop), enc, int(priority), int(sample_rate), float(speed))
         sid = C.c_uint64()
         self._check(self.lib.aur_submit(self.h, C.byref(d), C.byref(sid)))
         return sid.value
@@ -416,7 +427,7 @@ class NativeEngine:
         out = []
         for i in range(n.value):
             r = res[i]
-            nbytes = 4 * (r.n_samples + (r.n_latent_rows * 1024 if want_latents else 0))
+            nbytes = 4 * (r.n_samples + (r.n_latent_rows * 1024 if want_latents else 0)) + int(r.n_enc)   # the lease budget counts the stream too
             lease = None
             if not copy and nbytes:
                 with self._lease_lock:
@@ -428,7 +439,7 @@ class NativeEngine:
             def arr(ptr, shape):
                 if lease is None:
                     return np.ctypeslib.as_array(ptr, shape=shape).copy()
-                return np.asarray(_PinnedView(C.addressof(ptr.contents), shape, "<f4", lease))
+                return np.asarray(_PinnedView(C.addressof(ptr.contents), shape, "<f4" if ptr._type_ is C.c_float else "|u1", lease))
             item = {
                 "seq_id": r.seq_id,
                 "tokens": (np.ctypeslib.as_array(r.tokens, shape=(r.n_tokens,)).copy() if r.n_tokens
@@ -440,12 +451,34 @@ class NativeEngine:
             }
             if want_latents and r.n_latent_rows:
                 item["latents"] = arr(r.latents, (r.n_latent_rows, 1024))
+            if r.n_enc:   # aur_seq_desc.encoding: uint8 array (a view under the same lease when copy=False)
+                item["encoded"] = arr(r.enc, (int(r.n_enc),))
+                item["encoded_format"] = "flac"
             if lease is None:
                 self._check(self.lib.aur_release(self.h, r.seq_id))
             else:
                 item["lease"] = lease
             out.append(item)
         return out
+
+    def encode_flac(self, arrays, rates) -> List[bytes]:
+        """aur_encode_flac: finished float waveforms (one mono array each) with a sample rate per row -> 16-bit FLAC streams encoded on
+        the GPU, byte for byte flac.encode(codecs._to_int(x, 2), rate, 16).  1 <= samples <= 2^24 per row, rate < 2^20."""
+        arrs = [_f32(np.asarray(a).reshape(-1)) for a in arrays]
+        B = len(arrs)
+        if isinstance(rates, (int, np.integer)):
+            rates = [int(rates)] * B
+        if B == 0 or len(rates) != B:
+            raise ValueError("encode_flac: one sample rate per array, at least one array")
+        ptrs = (C.POINTER(C.c_float) * B)(*[_fp(a) for a in arrs])
+        ns = _i32([a.size for a in arrs])
+        sr = _i32([int(r) for r in rates])
+        stride = int(self.lib.aur_flac_bound(max(1, min(int(ns.max()), FLAC_MAX_SAMPLES))))
+        out = np.empty((B, stride), np.uint8)
+        lens = np.zeros(B, np.int64)
+        self._check(self.lib.aur_encode_flac(self.h, ptrs, _ip(ns), _ip(sr), B, out.ctypes.data_as(C.POINTER(C.c_uint8)), stride,
+                                             lens.ctypes.data_as(C.POINTER(C.c_int64))))
+        return [out[b, :int(lens[b])].tobytes() for b in range(B)]
 
     def release(self, seq_id: int):
         """Give a sequence's result block back now (after poll(copy=False)); the arrays over it must not be used afterwards.
@@ -743,6 +776,19 @@ class NativeEngine:
         self._check(self.lib.aur_dbg_conv_post(self.h, _fp(x), _fp(w), _ip(lens), B, cin, L, slope, int(bool(x_f16_act)), _fp(wav), sentinel,
                                                C.byref(bad)))
         return wav, int(bad.value)
+
+    def dbg_flac_encode(self, x, lens, rates, sentinel=0x5A):
+        """The FLAC kernels alone on x [B][stride] (lens[b] samples count, rates[b] Hz) -> (out [B][out_stride] uint8 that started as
+        `sentinel` bytes, out_lens [B]): stream b is out[b, :out_lens[b]], everything behind it must still be the sentinel."""
+        x = _f32(x)
+        B, stride = x.shape
+        lens, rates = _i32(lens), _i32(rates)
+        out_stride = int(self.lib.aur_flac_bound(int(lens.max())))
+        out = np.full((B, out_stride), sentinel, dtype=np.uint8)
+        out_lens = np.zeros(B, np.int32)
+        self._check(self.lib.aur_dbg_flac_encode(self.h, _fp(x), _ip(lens), _ip(rates), B, stride, out.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 out_stride, _ip(out_lens)))
+        return out, out_lens
 
     def dbg_resample_out(self, x, lens, rate, sentinel=-777.0):
         """The output-rate resampler alone on x [B][L] (L = max(lens)), rate [B] as aur_seq_desc.sample_rate.  Returns

@@ -23,6 +23,12 @@ class TTSOutput:
     start_time: Optional[float] = None
     end_time: Optional[float] = None
     token_length: Optional[int] = None
+    # new surface (TTSRequest.output_encoding): the engine's encoding of exactly `array` at `sample_rate` -- a uint8 view of the same
+    # result block (under the same lease) or bytes -- and its format ("flac": 16 bit).  to_bytes returns it for that format.  Every
+    # transform (resample, change_speed, from_tensor, combine_outputs of several outputs) yields an object without it; mutating `array`
+    # in place is NOT tracked: the stream then still encodes the samples the engine delivered.
+    encoded: Optional[Union[np.ndarray, bytes]] = None
+    encoded_format: Optional[str] = None
 
     def __post_init__(self):
         if isinstance(self.array, np.ndarray):
@@ -36,7 +42,8 @@ class TTSOutput:
             raise ValueError("combine_outputs needs at least one output")
         if len(outputs) == 1:   # a one-chunk request (every text up to the character limit): the chunk's own array, not a 1.25 MB copy of it
             o = outputs[0]
-            return TTSOutput(array=o.array, sample_rate=o.sample_rate, token_length=o.token_length or None, start_time=o.start_time)
+            return TTSOutput(array=o.array, sample_rate=o.sample_rate, token_length=o.token_length or None, start_time=o.start_time,
+                             encoded=o.encoded, encoded_format=o.encoded_format)
         return TTSOutput(array=np.concatenate([o.array for o in outputs]), sample_rate=outputs[0].sample_rate,
                          token_length=sum(o.token_length or 0 for o in outputs) or None,
                          start_time=outputs[0].start_time)
@@ -62,8 +69,12 @@ class TTSOutput:
         return n, self.sample_rate, n / float(self.sample_rate)
 
     def to_bytes(self, format: str = "wav", sample_width: int = 2) -> bytes:
-        """output.py:119-187: 'mp3', 'opus', 'aac', 'flac', 'wav', 'pcm'; samples clamped to [-1, 1]."""
+        """output.py:119-187: 'mp3', 'opus', 'aac', 'flac', 'wav', 'pcm'; samples clamped to [-1, 1].  An output that carries the
+        engine's own stream (`encoded`, TTSRequest.output_encoding) returns it for format "flac" at sample_width <= 2 (16 bit): the same
+        bytes the host writer would make of `array`, without running it."""
         from . import codecs
+        if self.encoded is not None and self.encoded_format == "flac" and format.lower() == "flac" and sample_width <= 2:
+            return self.encoded if isinstance(self.encoded, bytes) else np.asarray(self.encoded, dtype=np.uint8).tobytes()
         return codecs.encode(np.asarray(self.array, dtype=np.float32), self.sample_rate, format, sample_width,
                              bit_rate=self.bit_rate, compression=self.compression)
 

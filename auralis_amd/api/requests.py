@@ -1,8 +1,8 @@
 """TTSRequest — same fields, defaults and meaning as the reference dataclass
 (src/auralis/common/definitions/requests.py:134-277).  Fields the reference carries but never consumes on the
 synthesis path (do_sample, length_penalty, sound_norm_refs, load_sample_rate) are kept for
-drop-in compatibility.  `seed` is new surface (per-request noise stream; the reference has none); so are `priority`, `speed` and
-`output_sample_rate`."""
+drop-in compatibility.  `seed` is new surface (per-request noise stream; the reference has none); so are `priority`, `speed`,
+`output_sample_rate` and `output_encoding`."""
 from __future__ import annotations
 
 import copy as _copy
@@ -15,6 +15,8 @@ from .lang import get_language, validate_language
 
 # the rates the engine delivers (aur_seq_desc.sample_rate; include/auralis_amd.h)
 OUTPUT_SAMPLE_RATES = (8000, 16000, 22050, 24000, 32000, 44100, 48000)
+# what the engine encodes behind the vocoder (aur_seq_desc.encoding)
+OUTPUT_ENCODINGS = (None, "flac")
 
 
 @dataclass
@@ -64,8 +66,14 @@ class TTSRequest:
     # aur_seq_desc.sample_rate for every chunk -- the GPU resamples behind the vocoder (torchaudio's windowed sinc, the rule of the
     # reference's TTSOutput.resample) and stores the result where the 24 kHz waveform would have gone; nothing runs on the host
     output_sample_rate: int = 24000
+    # new surface, like `output_sample_rate`: None, or "flac" -- every chunk is also encoded to a 16-bit FLAC stream on the GPU behind
+    # the vocoder (aur_seq_desc.encoding) and its TTSOutput carries the bytes (`encoded`), which to_bytes("flac") then returns instead of
+    # running the host writer.  The float audio is delivered as ever
+    output_encoding: Optional[str] = None
 
     def __post_init__(self):
+        if self.output_encoding not in OUTPUT_ENCODINGS:
+            raise ValueError(f"output_encoding must be one of {OUTPUT_ENCODINGS}, got {self.output_encoding!r}")
         if isinstance(self.output_sample_rate, bool) or not isinstance(self.output_sample_rate, int) \
                 or self.output_sample_rate not in OUTPUT_SAMPLE_RATES:
             raise ValueError(f"output_sample_rate must be one of {OUTPUT_SAMPLE_RATES}, got {self.output_sample_rate!r}")

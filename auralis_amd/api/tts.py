@@ -82,7 +82,7 @@ class TTS:
     @staticmethod
     def split_requests(request: TTSRequest, max_length: int = 100000) -> List[TTSRequest]:
         """Texts longer than max_length become several requests with fresh ids (core/tts.py:236-255).  Every field follows the copy
-        (`speed`, `output_sample_rate`, the sampling parameters) except `priority`: latency-critical is the head of the text, the part a listener waits for,
+        (`speed`, `output_sample_rate`, `output_encoding`, the sampling parameters) except `priority`: latency-critical is the head of the text, the part a listener waits for,
         so only the first request keeps it."""
         if not isinstance(request.text, str) or len(request.text) <= max_length:
             return [request]

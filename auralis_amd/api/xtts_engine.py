@@ -320,7 +320,9 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
                        **({"speed": float(request.speed)} if getattr(request, "speed", 1.0) != 1.0 else {}),
                        # so does the output rate; 24000 leaves the keyword out (engines and test doubles without it keep working)
                        **({"sample_rate": int(request.output_sample_rate)}
-                          if getattr(request, "output_sample_rate", 24000) != 24000 else {}))
+                          if getattr(request, "output_sample_rate", 24000) != 24000 else {}),
+                       # and the encoding of the delivered audio (aur_seq_desc.encoding); unset leaves the keyword out too
+                       **({"encoding": str(request.output_encoding)} if getattr(request, "output_encoding", None) else {}))
             if self._placer is None:
                 fut = self.driver.submit(loop, reregister=lambda: self.native.set_conditioning(key, g_np, s_np), **seq)
             else:
@@ -408,7 +410,25 @@ class XTTSv2Engine(BaseAsyncTTSEngine):
         # of it and gives the block back when it is dropped (ResultLease); nothing is copied between the GPU's store and the caller
         yield TTSOutput(array=item["wav"], sample_rate=int(item.get("sample_rate", 24000)),
                         start_time=request.start_time if request is not None else None,
-                        token_length=int(len(item["tokens"])))
+                        token_length=int(len(item["tokens"])),
+                        # TTSRequest.output_encoding: the engine's stream of exactly this array, a view under the same lease
+                        encoded=item.get("encoded"), encoded_format=item.get("encoded_format"))
+
+    @property
+    def native_flac(self) -> bool:
+        """Every engine behind the plugin encodes FLAC on the GPU (aur_seq_desc.encoding, aur_encode_flac); test doubles may not."""
+        return all(hasattr(n, "encode_flac") for n in self.natives)
+
+    async def encode_flac(self, output: TTSOutput) -> bytes:
+        """The 16-bit FLAC stream of a finished waveform, encoded on the GPU by the one-shot entry (aur_encode_flac) of the least-loaded
+        engine, on a worker thread: the event loop never runs an encoder.  For audio the per-chunk encoding cannot cover (several chunks
+        joined by combine_outputs, a waveform reworked on the host)."""
+        native = self._least_loaded_native()
+        one_shot = getattr(native, "encode_flac", None)
+        if one_shot is None:
+            raise RuntimeError("the engine has no encode_flac entry point (aur_encode_flac)")
+        arr = np.asarray(output.array, dtype=np.float32).reshape(-1)
+        return (await asyncio.to_thread(one_shot, [arr], [int(output.sample_rate)]))[0]
 
     async def shutdown(self):
         if self._placer is not None:

@@ -11,8 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_C")
 LIB = os.path.join(OUT_DIR, "libauralis_amd.so")
-SOURCES = ["vocoder_kernels.hip", "gpt_kernels.hip", "cond_kernels.hip", "engine.hip", "dbg_harness.hip"]
-HEADERS = ["common.h", "vocoder_kernels.h", "gpt_kernels.h", "gemm_rows_kernel.inc", "cond_kernels.h", "cond_net.h", "dev_buf.h", "gpt_host.h", "gpt_net.h", "voc_net.h", "abi_internal.h", os.path.join("..", "..", "include", "auralis_amd.h")]
+SOURCES = ["vocoder_kernels.hip", "gpt_kernels.hip", "cond_kernels.hip", "flac_kernels.hip", "engine.hip", "dbg_harness.hip"]
+HEADERS = ["common.h", "vocoder_kernels.h", "gpt_kernels.h", "gemm_rows_kernel.inc", "cond_kernels.h", "cond_net.h", "flac_kernels.h", "dev_buf.h", "gpt_host.h", "gpt_net.h", "voc_net.h", "abi_internal.h", os.path.join("..", "..", "include", "auralis_amd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -amdgpu-kernarg-preload-count=16: the leading scalar kernel arguments (up to 14 dwords next to the kernarg pointer) arrive in SGPRs
 # with the wave instead of through dependent s_load round trips; a kernel whose firmware does not preload runs its compatibility

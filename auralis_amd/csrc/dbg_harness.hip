@@ -1,5 +1,5 @@
 // Kernel test harness: the aur_dbg_* entry points of include/auralis_amd.h that run ONE kernel on host arrays (tests/test_gpu_kernels.py,
-// test_gpu_prefill_kernels.py, test_gpu_vocoder_kernels.py, test_gpu_resample.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
+// test_gpu_prefill_kernels.py, test_gpu_vocoder_kernels.py, test_gpu_resample.py, test_gpu_flac.py, test_gpu_gpt.py, test_gpu_gpt_fp16.py).  They take from the engine its streams, its arithmetic mode and
 // the K-split scratch (DbgCtx) and nothing else, and the host rules of a launch from where the engine takes them: gpt_host.h (the decode
 // GEMMs' operands) and voc_net.h (the storage of a vocoder conv's tensors); aur_dbg_prefill and aur_dbg_sample drive real engine state
 // and live in engine.hip.
@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "abi_internal.h"
+#include "flac_kernels.h"
 #include "gpt_host.h"
 #include "voc_net.h"
 
@@ -818,6 +819,37 @@ int aur_dbg_resample_out(aur_engine* e, const float* x, const int32_t* lens, con
         launch_resample_out(dx.as<float>(), Ld, dl.as<int>(), 1, dc.as<int>(), dt.as<int>(), reinterpret_cast<float*>(go.data()), Lout, B, Lout,
                             c.st);
         *guard_changed = go.download(out, c.st);
+    });
+}
+int aur_dbg_flac_encode(aur_engine* e, const float* x, const int32_t* lens, const int32_t* rates, int32_t B, int64_t stride, uint8_t* out,
+                        int64_t out_stride, int32_t* out_lens) {
+    CHECK_PTR(e);
+    CHECK_PTR(x);
+    CHECK_PTR(lens);
+    CHECK_PTR(rates);
+    CHECK_PTR(out);
+    CHECK_PTR(out_lens);
+    return guarded([&] {
+        const DbgCtx c = use(e);
+        AUR_REQUIRE(B >= 1 && stride >= 1, "dbg_flac_encode: shapes");
+        for (int b = 0; b < B; ++b) AUR_REQUIRE(lens[b] >= 1 && lens[b] <= stride, "dbg_flac_encode: 1 <= lens[b] <= stride");
+        // guard | out rows (the caller's bytes) | guard
+        const uint8_t guard = 0xA5;
+        const size_t body = (size_t)B * out_stride;
+        std::vector<uint8_t> img(2 * kGuardBytes + body, guard);
+        std::memcpy(img.data() + kGuardBytes, out, body);
+        DevBuf dx, dout, dlen;
+        dx.upload(x, (size_t)B * stride * 4);
+        dout.upload(img);
+        dlen.ensure((size_t)B * 4);
+        FlacEncoder enc;
+        enc.encode(dx.as<float>(), stride, nullptr, std::vector<int>(lens, lens + B), std::vector<int>(rates, rates + B), dout.as<uint8_t>() + kGuardBytes,
+                   out_stride, dlen.as<int>(), c.st_lo);
+        download(img.data(), dout, img.size(), c.st_lo);
+        HIP_CHECK(hipMemcpy(out_lens, dlen.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+        std::memcpy(out, img.data() + kGuardBytes, body);
+        for (size_t i = 0; i < kGuardBytes; ++i)
+            if (img[i] != guard || img[kGuardBytes + body + i] != guard) throw HipError("dbg_flac_encode: a guard byte around the output rows changed");
     });
 }
 

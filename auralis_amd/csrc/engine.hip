@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <map>
@@ -21,6 +22,7 @@
 
 #include "abi_internal.h"
 #include "cond_net.h"
+#include "flac_kernels.h"
 #include "gpt_net.h"
 #include "voc_net.h"
 
@@ -54,6 +56,8 @@ struct Seq {
     int n_samples = 0;
     const float* latents = nullptr;   // into `result_block` (aur_config.return_latents)
     int n_latent_rows = 0;
+    const uint8_t* enc = nullptr;     // into `result_block` (aur_seq_desc.encoding)
+    int64_t n_enc = 0;
     PinBlock* result_block = nullptr;
     int pool_idx = -1;   // latent-pool entry once the tokens are done (vocoder stage)
     bool shared_prefix = false;
@@ -410,6 +414,7 @@ public:
         AUR_REQUIRE(d.repetition_penalty > 0.f, "repetition_penalty > 0");
         AUR_REQUIRE(speed_valid(d.speed), "speed is 0 (unset) or in [0.5, 2.0]");
         AUR_REQUIRE(rate_class(d.sample_rate) >= 0, "sample_rate is 0 (unset) or one of 8000, 16000, 22050, 24000, 32000, 44100, 48000");
+        AUR_REQUIRE(d.encoding == 0 || d.encoding == AUR_ENC_FLAC16, "encoding is 0 (none) or AUR_ENC_FLAC16");
         std::lock_guard<std::mutex> lk(mu_);
         {   // reject bad text ids / positions here, not in the middle of a batched prefill
             if (!w_.has("text_emb") || !w_.has("text_pos")) throw StateError("weights not loaded");
@@ -455,6 +460,8 @@ public:
             r.latents = s->latents;
             r.error = s->error;
             r.sample_rate = s->params.sample_rate ? s->params.sample_rate : 24000;
+            r.enc = s->enc;
+            r.n_enc = s->n_enc;
         }
         return n;
     }
@@ -485,7 +492,7 @@ public:
     void finish_cancelled(Seq* s) {
         s->cancel = true;
         s->error = AUR_E_CANCELLED;
-        s->wav = nullptr; s->n_samples = 0; s->latents = nullptr; s->n_latent_rows = 0;
+        s->wav = nullptr; s->n_samples = 0; s->latents = nullptr; s->n_latent_rows = 0; s->enc = nullptr; s->n_enc = 0;
         spk_info_[s->spk_row].refs--;
         s->state = SeqState::DONE;
         done_.push_back(s);
@@ -556,7 +563,7 @@ public:
             if (s->slot >= 0) slot_owner_[s->slot] = nullptr;
             s->slot = -1;
             s->error = code;
-            s->wav = nullptr; s->n_samples = 0; s->latents = nullptr; s->n_latent_rows = 0;
+            s->wav = nullptr; s->n_samples = 0; s->latents = nullptr; s->n_latent_rows = 0; s->enc = nullptr; s->n_enc = 0;
             spk_info_[s->spk_row].refs--;
             s->state = SeqState::DONE;
             done_.push_back(s);
@@ -766,6 +773,38 @@ public:
             HIP_CHECK(hipMemcpy(wav_out + (long)b * wav_stride, tmp_wav_.as<float>() + (long)b * max_samples,
                                 (size_t)ns * sizeof(float), hipMemcpyDeviceToHost));
             if (n_samples_out) n_samples_out[b] = ns;
+        }
+    }
+
+    // ------------------------------------------------------------------ standalone FLAC encoder (aur_encode_flac)
+    void encode_flac(const float* const* x, const int32_t* n, const int32_t* rate, int B, uint8_t* out, int64_t out_stride, int64_t* out_lens) {
+        std::lock_guard<std::mutex> gl(gpu_mu_);   // not while a step is running (shares the vocoder stream, in order behind a pass in flight)
+        use();
+        AUR_REQUIRE(B >= 1, "encode_flac: B >= 1");
+        std::vector<int> len(n, n + B), sr(rate, rate + B);
+        long max_n = 0;
+        for (int b = 0; b < B; ++b) {
+            AUR_REQUIRE(x[b], "encode_flac: null row");
+            AUR_REQUIRE(len[b] >= 1 && len[b] <= kFlacMaxSamples, "encode_flac: 1 <= samples <= 2^24 per row");
+            AUR_REQUIRE(sr[b] >= 1 && sr[b] < kFlacMaxRate, "encode_flac: 1 <= sample rate < 2^20");
+            for (int i = 0; i < len[b]; ++i) AUR_REQUIRE(std::isfinite(x[b][i]), "encode_flac: samples must be finite");
+            max_n = std::max(max_n, (long)len[b]);
+        }
+        const long bound = flac_stream_bound(max_n), ostride = (bound + 15) & ~15L, xstride = (max_n + 3) & ~3L;
+        AUR_REQUIRE(out_stride >= bound, "encode_flac: out_stride must hold aur_flac_bound(longest row)");
+        flac_x_.ensure((size_t)B * xstride * 4);
+        flac_out_.ensure((size_t)B * ostride + (size_t)B * 4);
+        for (int b = 0; b < B; ++b)
+            HIP_CHECK(hipMemcpyAsync(flac_x_.as<float>() + (size_t)b * xstride, x[b], (size_t)len[b] * 4, hipMemcpyHostToDevice, st_voc_));
+        int* d_len = reinterpret_cast<int*>(flac_out_.as<uint8_t>() + (size_t)B * ostride);
+        flac_host_.encode(flac_x_.as<float>(), xstride, nullptr, len, sr, flac_out_.as<uint8_t>(), ostride, d_len, st_voc_);
+        std::vector<int> got(B);
+        HIP_CHECK(hipMemcpyAsync(got.data(), d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st_voc_));
+        HIP_CHECK(hipStreamSynchronize(st_voc_));
+        for (int b = 0; b < B; ++b) {
+            if (got[b] < kFlacHeader || got[b] > flac_stream_bound(len[b])) throw HipError("encode_flac: stream length out of range");
+            HIP_CHECK(hipMemcpy(out + (size_t)b * out_stride, flac_out_.as<uint8_t>() + (size_t)b * ostride, (size_t)got[b], hipMemcpyDeviceToHost));
+            out_lens[b] = got[b];
         }
     }
 
@@ -1117,7 +1156,22 @@ private:
         }
         if (fail_at_voc_ > 0 && --fail_at_voc_ == 0)   // AUR_TEST_FAIL_VOC=n: fault injection inside the n-th vocoder launch
             throw HipError("injected failure (AUR_TEST_FAIL_VOC)");
-        voc_block_->buf.ensure((size_t)B * voc_max_samples_ * 4 + (cfg_.return_latents ? (size_t)B * kMaxLatRows * kHidden * 4 : 0));
+        // aur_seq_desc.encoding: the rows that also leave as FLAC streams.  Block layout: float rows | latents | streams (one row per
+        // encoded utterance at voc_enc_stride_ = the longest one's bound, 42 + frames * 8205) | their lengths.  A pass without such a
+        // row is what it was: same launches, same arguments, nothing allocated.
+        voc_enc_rows_.clear();
+        std::vector<int> enc_len, enc_rate;
+        voc_enc_stride_ = 0;
+        for (int b = 0; b < B; ++b)
+            if (voc_batch_[b]->params.encoding) {
+                voc_enc_rows_.push_back(b);
+                enc_len.push_back(out_samples(voc_nl_[b], voc_speed_[b], voc_rate_[b]));
+                enc_rate.push_back(voc_rate_[b] ? voc_rate_[b] : 24000);
+                voc_enc_stride_ = std::max(voc_enc_stride_, (flac_stream_bound(enc_len.back()) + 15) & ~15L);
+            }
+        const size_t wav_bytes = (size_t)B * voc_max_samples_ * 4, lat_bytes = cfg_.return_latents ? (size_t)B * kMaxLatRows * kHidden * 4 : 0;
+        const size_t n_enc = voc_enc_rows_.size(), enc_bytes = n_enc * (size_t)voc_enc_stride_;
+        voc_block_->buf.ensure(wav_bytes + lat_bytes + enc_bytes + n_enc * 4);
         HIP_CHECK(hipStreamWaitEvent(st_voc_, ev_lat_, 0));   // latents parked by the main stream
         // The waveform goes straight into the pinned result block: conv_post (Cin -> 1, + tanh: 0.4 ms of HBM-bound work per 64
         // utterances) stores its samples over PCIe -- coalesced 1 KiB per workgroup -- instead of into device memory with one D2H copy
@@ -1125,9 +1179,24 @@ private:
         // decode step being over).  hipHostMalloc memory is device-visible and coherent; the event below orders the host's reads.
         float* hw = voc_block_->buf.as<float>();
         float* hl = hw + (size_t)B * voc_max_samples_;
-        voc_->forward(B, voc_nl_, voc_speed_, voc_rate_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, hw, voc_max_samples_,
+        // an encoded pass keeps the delivered waveform in device memory for the encoder; the float rows follow in one copy (same bits)
+        float* wav_dst = hw;
+        if (n_enc) {
+            voc_dev_wav_.ensure(wav_bytes);
+            wav_dst = voc_dev_wav_.as<float>();
+        }
+        voc_->forward(B, voc_nl_, voc_speed_, voc_rate_, latpool_.as<float>(), (long)kMaxLatRows * kHidden, &rows, cond, wav_dst, voc_max_samples_,
                       voc_cond_.as<float>(), cfg_.profile != 0);
         stats_.vocoder_batches++;
+        if (n_enc) {
+            HIP_CHECK(hipMemcpyAsync(hw, wav_dst, wav_bytes, hipMemcpyDeviceToHost, st_voc_));
+            voc_dev_enc_.ensure(enc_bytes + n_enc * 4);
+            uint8_t* d_enc = voc_dev_enc_.as<uint8_t>();
+            flac_pass_.encode(wav_dst, voc_max_samples_, &voc_enc_rows_, enc_len, enc_rate, d_enc, voc_enc_stride_,
+                              reinterpret_cast<int*>(d_enc + enc_bytes), st_voc_);
+            HIP_CHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(hw) + wav_bytes + lat_bytes, d_enc, enc_bytes + n_enc * 4, hipMemcpyDeviceToHost,
+                                     st_voc_));
+        }
         for (int b = 0; b < B && cfg_.return_latents; ++b)
             HIP_CHECK(hipMemcpyAsync(hl + (size_t)b * kMaxLatRows * kHidden,
                                      latpool_.as<float>() + (long)rows[b] * kMaxLatRows * kHidden,
@@ -1149,6 +1218,16 @@ private:
         const int B = (int)voc_batch_.size();
         const float* hw = voc_block_->buf.as<float>();
         const float* hl = hw + (size_t)B * voc_max_samples_;
+        const uint8_t* he = reinterpret_cast<const uint8_t*>(hw) + (size_t)B * voc_max_samples_ * 4 +
+                            (cfg_.return_latents ? (size_t)B * kMaxLatRows * kHidden * 4 : 0);
+        const int* he_len = reinterpret_cast<const int*>(he + voc_enc_rows_.size() * (size_t)voc_enc_stride_);
+        // (before any sequence is handed its result: a throw here fails the whole batch like any other collect error)
+        for (size_t i = 0; i < voc_enc_rows_.size(); ++i) {
+            const int b = voc_enc_rows_[i];
+            if (he_len[i] < kFlacHeader || he_len[i] > flac_stream_bound(out_samples(voc_nl_[b], voc_speed_[b], voc_rate_[b])))
+                throw HipError("FLAC stream length out of range");
+        }
+        size_t ei = 0;
         for (int b = 0; b < B; ++b) {
             Seq* s = voc_batch_[b];
             const int ns = out_samples(voc_nl_[b], voc_speed_[b], voc_rate_[b]);   // delivered samples, at the sequence's rate
@@ -1159,6 +1238,11 @@ private:
                 s->n_latent_rows = voc_nl_[b];
             }
             stats_.samples_generated += ns;
+            if (ei < voc_enc_rows_.size() && voc_enc_rows_[ei] == b) {
+                s->enc = he + ei * (size_t)voc_enc_stride_;
+                s->n_enc = he_len[ei];
+                ++ei;
+            }
             std::lock_guard<std::mutex> lk(mu_);
             s->result_block = voc_block_;
             voc_block_->refs++;
@@ -1219,6 +1303,11 @@ private:
     std::vector<int> voc_rate_;         // aur_seq_desc.sample_rate of the batch's sequences
     bool voc_split_rest_ = false;       // the last pass left part of the queue behind because of the workspace bound
     int voc_max_samples_ = 0;
+    std::vector<int> voc_enc_rows_;     // rows of the batch with aur_seq_desc.encoding, ascending
+    long voc_enc_stride_ = 0;           // bytes per stream row of the batch's result block
+    DevBuf voc_dev_wav_, voc_dev_enc_;  // an encoded pass: the delivered waveform and the streams in device memory
+    FlacEncoder flac_pass_, flac_host_; // the vocoder pass's encoder and aur_encode_flac's (each with its scratch)
+    DevBuf flac_x_, flac_out_;          // aur_encode_flac's device copies
     bool voc_active_ = false;
     std::vector<std::unique_ptr<PinBlock>> result_blocks_;   // pool; a block is free when refs == 0 (guarded by mu_)
     PinBlock* voc_block_ = nullptr;                          // block of the in-flight vocoder batch
@@ -1351,6 +1440,17 @@ int aur_compute_conditioning(aur_engine* e, const float* const* pcm, const int32
     CHECK_PTR(out_gpt_cond);
     CHECK_PTR(out_spk_emb);
     return bound(e, [&] { e->impl.compute_conditioning(pcm, n_samples, n_refs, *p, out_gpt_cond, out_spk_emb); });
+}
+int64_t aur_flac_bound(int64_t n_samples) { return n_samples < 0 ? 0 : aur::flac_stream_bound(n_samples); }
+int aur_encode_flac(aur_engine* e, const float* const* x, const int32_t* n, const int32_t* rate, int32_t B, uint8_t* out, int64_t out_stride,
+                    int64_t* out_lens) {
+    CHECK_PTR(e);
+    CHECK_PTR(x);
+    CHECK_PTR(n);
+    CHECK_PTR(rate);
+    CHECK_PTR(out);
+    CHECK_PTR(out_lens);
+    return bound(e, [&] { e->impl.encode_flac(x, n, rate, B, out, out_stride, out_lens); });
 }
 int aur_submit(aur_engine* e, const aur_seq_desc* seq, uint64_t* seq_id) {
     CHECK_PTR(e);

@@ -171,6 +171,9 @@ async def run_unless_disconnected(http_request: Any, awaitable, poll_s: float = 
             task.cancel()
 
 
+FLAC_ONE_SHOT_MAX_SAMPLES = 1 << 24   # aur_encode_flac's limit per waveform (include/auralis_amd.h)
+
+
 def create_app(tts: Optional[TTS], speed_mode: str = "stretch", sample_rate: int = 24000) -> FastAPI:
     """`speed_mode`: what the OpenAI `speed` field of /v1/audio/speech does.  "stretch" (default, the reference's behaviour): the
     finished waveform goes through TTSOutput.change_speed, a phase vocoder on the host.  "latent": the value, clamped to [0.5, 2.0],
@@ -185,6 +188,22 @@ def create_app(tts: Optional[TTS], speed_mode: str = "stretch", sample_rate: int
     app.state.speed_mode = speed_mode
     app.state.sample_rate = sample_rate
 
+    def _engine_encodes(tts_engine) -> bool:
+        """the engine plugin has the GPU encoder: its own word (XTTSv2Engine.native_flac), else the presence of encode_flac"""
+        native = getattr(tts_engine, "native_flac", None)
+        return hasattr(tts_engine, "encode_flac") if native is None else bool(native)
+
+    async def _flac_bytes(engine: TTS, output) -> bytes:
+        """The response body of response_format="flac" (16 bit).  The engine's own stream when the output carries one (a one-chunk
+        request); else the engine's one-shot GPU encoder (several chunks joined, a waveform reworked by stretch mode), awaited on the
+        facade's loop; else, for an engine without that entry or a waveform outside its limits, the host writer on a worker thread.  Never the host writer on this loop."""
+        if getattr(output, "encoded", None) is not None and getattr(output, "encoded_format", None) == "flac":
+            return output.to_bytes("flac")   # (hands the stream back; no encoder runs)
+        # (outside aur_encode_flac's limits -- an empty waveform, more than 2^24 samples: some 11.6 min at 24 kHz -- the host writer serves)
+        if _engine_encodes(engine.tts_engine) and 1 <= len(output.array) <= FLAC_ONE_SHOT_MAX_SAMPLES:
+            return await asyncio.wrap_future(asyncio.run_coroutine_threadsafe(engine.tts_engine.encode_flac(output), engine._loop))
+        return await asyncio.to_thread(output.to_bytes, "flac")
+
     @app.post("/v1/audio/speech")
     async def generate_audio(request: AudioSpeechGenerationRequest, http_request: Request):
         engine: Optional[TTS] = app.state.tts
@@ -195,14 +214,22 @@ def create_app(tts: Optional[TTS], speed_mode: str = "stretch", sample_rate: int
             tts_request = request.to_tts_request(sample_rate)   # (an unsupported rate: ValueError, the envelope below)
             if speed_mode == "latent":
                 tts_request.speed = min(2.0, max(0.5, float(request.speed)))
+            # flac: the engine encodes every chunk on the GPU behind the vocoder (TTSRequest.output_encoding), unless the waveform
+            # will be reworked on the host afterwards (stretch mode at another speed than 1)
+            reworked = speed_mode == "stretch" and request.speed != 1.0
+            if request.response_format == "flac" and not reworked and _engine_encodes(engine.tts_engine):
+                tts_request.output_encoding = "flac"
             fut = asyncio.run_coroutine_threadsafe(engine.generate_speech_async(tts_request), engine._loop)
             try:
                 output = await run_unless_disconnected(http_request, asyncio.wrap_future(fut))
             except ClientDisconnected:
                 return Response(status_code=499)   # (nobody reads it; nginx's "client closed request")
-            if speed_mode == "stretch" and request.speed != 1.0:
+            if reworked:
                 output = output.change_speed(request.speed)
-            data = output.to_bytes(request.response_format)
+            if request.response_format == "flac":
+                data = await _flac_bytes(engine, output)
+            else:
+                data = output.to_bytes(request.response_format)
             return Response(content=data, media_type=_MEDIA[request.response_format])
         except Exception as e:  # same envelope as the reference (oai_server.py:92-93)
             return JSONResponse(status_code=500, content={"error": f"Error generating audio: {e}"})

@@ -109,6 +109,10 @@ typedef struct aur_seq_desc {
     int32_t max_tokens;       /* gpt_max_audio_tokens (605) */
     uint32_t seed;            /* per-sequence noise stream (new surface; reference has none) */
     int32_t ignore_stop;      /* 1 = fixed-length mode for timing (stop id does not end the sequence) */
+    int32_t encoding;         /* 0 = none; AUR_ENC_FLAC16 = also encode the delivered waveform (after speed and sample_rate, at the delivered
+                                 rate) to a 16-bit FLAC stream on the GPU behind the vocoder: aur_result.enc / n_enc, the bytes aur_encode_flac
+                                 gives for aur_result.wav.  Anything else makes aur_submit fail with AUR_E_INVALID.  New surface; tokens,
+                                 latents and wav do not depend on it.  Such a pass pins about half as many host bytes again */
     int32_t priority;         /* 0 = normal; > 0 = latency-critical (the chunk a listener is waiting for: the head of a stream; the
                                  reference has no counterpart, its streaming latency is whatever vLLM's FIFO gives,
                                  tests/integration/stream_ttfb.py:24-37).  It is admitted in front of the normal queue and at once,
@@ -135,6 +139,7 @@ typedef struct aur_seq_desc {
                                  256 * floor(4 L0' * 24000 / 22050) samples at unchanged pitch.  Decoding does not depend on it:
                                  tokens, aur_result.latents and n_latent_rows are those of speed 1 */
 } aur_seq_desc;
+#define AUR_ENC_FLAC16 1
 
 /* Finished sequence.  Pointers stay valid until aur_release(seq_id).  Replaces the RequestOutput consumed at
  * XTTSv2.py:785 and the TTSOutput array built at XTTSv2.py:804-811. */
@@ -147,6 +152,8 @@ typedef struct aur_result {
     int32_t n_latent_rows;
     const float* latents;     /* [n_tokens][1024] vocoder input (final_norm applied twice), may be NULL */
     int32_t error;            /* 0 or AUR_E_* if this sequence failed */
+    const uint8_t* enc;       /* aur_seq_desc.encoding: the encoded stream of wav (n_enc bytes), valid until aur_release; else NULL */
+    int64_t n_enc;
     int32_t sample_rate;      /* of wav, in Hz: aur_seq_desc.sample_rate, 24000 when that was 0 */
 } aur_result;
 
@@ -304,6 +311,17 @@ int aur_vocode_speed(aur_engine* e, const float* latents, const int32_t* n_lat, 
 int aur_vocode_rate(aur_engine* e, const float* latents, const int32_t* n_lat, const float* speed, const int32_t* sample_rate, int32_t B,
                     int32_t t_max, uint64_t speaker_key, float* wav_out, int64_t wav_stride, int32_t* n_samples_out);
 
+/* FLAC on the GPU: B finished float waveforms x[b] (n[b] mono samples in HOST memory, rate[b] Hz) -> B complete 16-bit FLAC streams,
+ * byte for byte what the host writer gives (auralis_amd/api/flac.py: flac.encode(codecs._to_int(x, 2), rate, 16)): samples clamped
+ * to [-1, 1], * 32767 in fp32, converted toward zero; 4096-sample blocks; CONSTANT, VERBATIM or FIXED (order 0..4) subframes with
+ * partitioned Rice codes; MD5 of the PCM in STREAMINFO.  Replaces torchaudio.save(format="flac") of TTSOutput.to_bytes (output.py:119-187).
+ * Stream b goes to out + b * out_stride (out_lens[b] bytes; nothing past them is written); out_stride must hold
+ * aur_flac_bound(max n[b]).  1 <= n[b] <= 2^24, 1 <= rate[b] < 2^20 and the samples finite, anything else is AUR_E_INVALID.  Takes
+ * the GPU between steps, as aur_compute_conditioning does.  aur_flac_bound(n) = 42 + ceil(n / 4096) * 8205. */
+int64_t aur_flac_bound(int64_t n_samples);
+int aur_encode_flac(aur_engine* e, const float* const* x, const int32_t* n, const int32_t* rate, int32_t B, uint8_t* out, int64_t out_stride,
+                    int64_t* out_lens);
+
 int aur_sync(aur_engine* e);
 int aur_get_stats(aur_engine* e, aur_stats* out);
 int aur_reset_stats(aur_engine* e);
@@ -424,6 +442,12 @@ int aur_dbg_conv_post(aur_engine* e, const float* x, const float* w, const int32
  * Lout = the longest of them.  In / out sentinel and guards as above. */
 int aur_dbg_resample_out(aur_engine* e, const float* x, const int32_t* lens, const int32_t* rate, int32_t B, int32_t L, float* out,
                          int32_t Lout, float guard_value, int64_t* guard_changed);
+/* The FLAC kernels alone (flac_md5_kernel, flac_frame_kernel, flac_assemble_kernel): x [B][stride] rows of which lens[b] >= 1 samples
+ * count (what a row holds past them must not matter), rates[b] Hz.  out [B][out_stride] bytes is IN/OUT (the caller's content is
+ * uploaded first, so that what the kernels leave alone comes back unchanged) and sits between two guards on the device; a changed guard
+ * is AUR_E_HIP.  out_lens[b] = bytes of stream b; out_stride >= aur_flac_bound(max lens). */
+int aur_dbg_flac_encode(aur_engine* e, const float* x, const int32_t* lens, const int32_t* rates, int32_t B, int64_t stride, uint8_t* out,
+                        int64_t out_stride, int32_t* out_lens);
 /* Prefill one prompt and return ln_f rows [n_rows][1024] and the penalised logits [1026] of the last row. */
 int aur_dbg_prefill(aur_engine* e, const int32_t* text_ids, int32_t n_text, uint64_t speaker_key,
                     float repetition_penalty, float* lnf_rows_out, float* logits_out);
